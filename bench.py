@@ -1,9 +1,16 @@
 #!/usr/bin/env python
 """bench.py -- the benchmarks of the CHORE field-query / fitting hot path on MI355X, one JSON line each.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode all|query|fit|train]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode all|query|fit|train] [--full] [--dump-outputs DIR]
 
---mode all (default, what the driver runs): the line of --mode query (the K timed steps are query steps) and, measured after
+A plain run (no --full) of --mode all or --mode query measures the headline only: set up, W warm-up steps, the K timed query
+    steps, the outputs if --dump-outputs is given, the line (metric, value, unit, dtype, ms_per_step, ...).  Nothing else runs.
+--full: everything else the benchmark measures and checks, after the timed region, as listed below.  --mode fit and
+    --mode train print their whole records either way.
+--dump-outputs DIR: after the timed steps, rank 0 writes what its last timed query step computed -- df, pca, parts, centers
+    of CHORE.get_preds(), float32 -- as DIR/<name>.npy.  The inputs are seeded: the same arguments give the same inputs.
+
+--mode all (default) with --full: the line of --mode query (the K timed steps are query steps) and, measured after
     the timed region by the same functions, the sub-records "fit" (metric 2) and "train" (metric 3), each with its own value,
     roofline and cpu_baseline, plus query_fwd_bwd_points_per_s (metric 1(ii): forward + backward to the points).  With
     N > 1 the "train" record is DDP over RCCL and carries the all-reduce share (a synced step against a no_sync() step);
@@ -28,7 +35,7 @@ steps bracketed by barrier + synchronize on both sides, MAX over ranks, rank 0 p
 image / frame: every rank runs the same per-GPU workload on its own seeded inputs ("scaling": "weak"); the
 only collectives are the barriers, the MAX-reduce of the time and, in train mode, DDP's gradient all-reduce.
 
-Extra objects in the line:
+Extra objects in the line (--full):
   roofline            query: the kernel class with the largest measured time per step -- ALGORITHMIC FLOPs per launch /
                       average launch duration measured live with hipEvents on the launch stream (chore_profile_enable;
                       that pass runs the encoder on ONE stream so kernels do not overlap) against the dense MFMA peak of
@@ -183,13 +190,14 @@ def self_launch(n):
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execv(sys.executable, cmd)
+    import subprocess
+    raise SystemExit(subprocess.call(cmd))        # a child process, not exec: this one has loaded torch
 
 
 class Ctx:
     """rank / device / collectives of this process"""
 
-    def __init__(self, gpus, backend=None, one_rank_group=False):
+    def __init__(self, gpus, backend=None, one_rank_group=False, use_gpu=True):
         self.world = int(os.environ.get("WORLD_SIZE", "1"))
         self.rank = int(os.environ.get("RANK", "0"))
         self.local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -203,7 +211,7 @@ class Ctx:
             faulthandler.dump_traceback_later(int(os.environ.get("CHORE_BENCH_REHEARSAL_DUMP_S", "600")), repeat=True)     # where a hung rank is
         if self.world != gpus:
             raise SystemExit(f"--gpus {gpus} but WORLD_SIZE={self.world}")
-        self.cuda = torch.cuda.is_available()
+        self.cuda = use_gpu and torch.cuda.is_available()
         self.dist = None
         if self.cuda:
             torch.cuda.set_device(self.local)
@@ -369,6 +377,23 @@ def emit_line(out, stream):
     print(s, file=stream, flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(d, named):
+    """--dump-outputs: each tensor of `named` as d/<name>.npy in float32.  Over DUMP_LIMIT_BYTES in all, the same seeded
+    sample of the last axis (the points) is written for every tensor -- the same arguments give the same sample."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: t.detach().float().cpu().numpy() for k, t in named.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = min(a.shape[-1] for a in arrays.values())
+        keep = np.sort(np.random.RandomState(0).choice(n, n * DUMP_LIMIT_BYTES // total, replace=False))
+        arrays = {k: np.ascontiguousarray(a[..., keep]) for k, a in arrays.items()}
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+
+
 # ---- mode: query ------------------------------------------------------------------------------------------------------
 def mode_query(args, ctx):
     from chore_amd import _lib
@@ -393,6 +418,24 @@ def mode_query(args, ctx):
             net.filter(images)
             net.query(points, crop_center=cc)
         return net, images, points, cc, step
+
+    def headline(elapsed, issue, in_flight, **config):
+        return base_line(args, ctx, "query-points/sec (HGFilters encode + 20k-pt MLP field query per 512x512 image)",
+                         ctx.world * B * N * args.steps / elapsed, "points/s", elapsed, True, args.dtype,
+                         dict({"workload": "BASELINE configs[1]: encode %dx(5,512,512) + query %dx%d points per GPU per step"
+                                           % (B, B, N),
+                               "precision": {"fp16x3": "fp32 tensors; the encoder's convolutions as three fp16 MFMAs per product on hi/lo "
+                                                       "split operands, fp32 accumulation (fp32-grade: meets the 1e-4 field tolerance); "
+                                                       "BASELINE names bf16 for this config -- that mode is in other_modes with its error",
+                                             "bf16": "bf16 feature maps and MFMA operands in the encoder, fp32 accumulation (a 1e-2 mode); heads fp32-grade",
+                                             "fp16": "IEEE half feature maps (BASELINE configs[4]'s 'fp16 fields'); convolutions as two fp16 MFMAs per "
+                                                     "product (activation x weight hi, lo), fp32 accumulation (a 1e-3 mode); heads fp32-grade",
+                                             "fp32": "fp32 tensors, native fp32 MFMA"}[args.dtype],
+                               "images_per_gpu": B, "points_per_image": N, "image": "512x512x5", "step_issue": issue,
+                               "batches_in_flight": in_flight,
+                               "heads_dtype": "fp32 results on the fp16 matrix cores, hi/lo split operands" if args.dtype != "fp32"
+                                              else "fp32 (native fp32 MFMA)", "sharding": "images across ranks, no collective"},
+                              **config))
 
     net, images, points, cc, step = make(args.dtype, rank)
     with torch.no_grad():
@@ -462,6 +505,15 @@ def mode_query(args, ctx):
                 graphs = []
                 issue = "eager launches from Python (graph capture failed: %s)" % repr(e)[:120]
         elapsed = ctx.timed(run, args.steps, args.warmup)
+        if args.dump_outputs and rank == 0:
+            # the outputs of the last timed step: the recording the round robin replayed last, the one recording, or the eager step's
+            if len(graphs) > 1:
+                preds = graphs[(counter[0] - 1) % len(graphs)][2]
+            else:
+                preds = graphs[0][2] if graphs else net.get_preds()
+            dump_outputs(args.dump_outputs, dict(zip(("df", "pca", "parts", "centers"), preds)))
+        if not args.full:
+            return headline(elapsed, issue, max(1, len(graphs))) if rank == 0 else None
         if len(graphs) > 1:
             single_elapsed = ctx.timed(graphs[0][0].replay, args.steps, 2)
             # every recording's outputs against an eager step's, after one more pipelined round
@@ -659,27 +711,13 @@ def mode_query(args, ctx):
                 "flops_per_launch": dv["tflops"] * 1e9 * dv["ms_per_step"] / dv["launches_per_step"]}
         if dom_dtype == "fp16x3":     # every algorithmic product is three fp16 MFMAs: the share of the matrix cores' issue rate
             roof["mfma_issue_frac"] = 3.0 * roof["frac"]
-        out = base_line(args, ctx, "query-points/sec (HGFilters encode + 20k-pt MLP field query per 512x512 image)",
-                        ctx.world * B * N * args.steps / elapsed, "points/s", elapsed, True, args.dtype,
-                        {"workload": "BASELINE configs[1]: encode %dx(5,512,512) + query %dx%d points per GPU per step"
-                                     % (B, B, N),
-                         "precision": {"fp16x3": "fp32 tensors; the encoder's convolutions as three fp16 MFMAs per product on hi/lo "
-                                                 "split operands, fp32 accumulation (fp32-grade: meets the 1e-4 field tolerance); "
-                                                 "BASELINE names bf16 for this config -- that mode is in other_modes with its error",
-                                       "bf16": "bf16 feature maps and MFMA operands in the encoder, fp32 accumulation (a 1e-2 mode); heads fp32-grade",
-                                       "fp16": "IEEE half feature maps (BASELINE configs[4]'s 'fp16 fields'); convolutions as two fp16 MFMAs per "
-                                               "product (activation x weight hi, lo), fp32 accumulation (a 1e-3 mode); heads fp32-grade",
-                                       "fp32": "fp32 tensors, native fp32 MFMA"}[args.dtype],
-                         "images_per_gpu": B, "points_per_image": N, "image": "512x512x5", "step_issue": issue, "batches_in_flight": max(1, len(graphs)),
-                         "heads_dtype": "fp32 results on the fp16 matrix cores, hi/lo split operands" if args.dtype != "fp32"
-                                        else "fp32 (native fp32 MFMA)", "sharding": "images across ranks, no collective",
-                         "field_err": field_err,
-                         "field_err_note": "max / mean absolute and relative-L2 difference to the values THE REFERENCE "
-                                           "produced for the same images and points (tests/golden/config2_fields.npz): 768 "
-                                           "of the 20 000 points of each of the 4 images are reference-checked value by value; "
-                                           "field_err.all_points_block_means covers ALL 80 000 points through the reference's sums "
-                                           "over blocks of 32 consecutive points (tests/golden/config2_blocksums.npz): the largest "
-                                           "deviation of a block's mean; stated tolerances: chore_amd/utils/field_check.py"})
+        out = headline(elapsed, issue, max(1, len(graphs)), field_err=field_err,
+                       field_err_note="max / mean absolute and relative-L2 difference to the values THE REFERENCE "
+                                      "produced for the same images and points (tests/golden/config2_fields.npz): 768 "
+                                      "of the 20 000 points of each of the 4 images are reference-checked value by value; "
+                                      "field_err.all_points_block_means covers ALL 80 000 points through the reference's sums "
+                                      "over blocks of 32 consecutive points (tests/golden/config2_blocksums.npz): the largest "
+                                      "deviation of a block's mean; stated tolerances: chore_amd/utils/field_check.py")
         single_ms = None if single_elapsed is None else single_elapsed / args.steps * 1e3
         out.update({"roofline": roof, "other_modes": other_modes, "encode_ms": enc_ms, "query_ms": qry_ms,
                     "eager_ms_per_step": eager_elapsed / args.steps * 1e3,
@@ -1153,7 +1191,9 @@ def mode_train(args, ctx):
 
 
 def mode_all(args, ctx):
-    """the query line with the fit and training records inside (what the driver's one command measures)"""
+    """the query line; with --full, the fit and training records inside it"""
+    if not args.full:
+        return mode_query(args, ctx)
     import copy
     _stage(ctx, "all: query")
     out = mode_query(args, ctx)
@@ -1257,7 +1297,16 @@ def main():
                     help="training, segmented arena: one all_reduce per segment, or reduce_scatter + all_gather")
     ap.add_argument("--train-other-modes", action="store_true", help="train mode: also time the other precision modes and measure every mode's gradient error")
     ap.add_argument("--dry-run", action="store_true", help="launch / rendezvous / timing skeleton only (no GPU needed): CPU + gloo")
+    ap.add_argument("--full", action="store_true",
+                    help="mode all / query: after the timed steps also measure and check everything else (component and kernel timings, "
+                         "roofline, field errors, other precisions, CPU baselines; mode all: the fit and train records)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="mode all / query: write the outputs of the last timed step (df, pca, parts, centers; float32) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_outputs and (args.mode in ("fit", "train") or args.dry_run):
+        ap.error("--dump-outputs writes the query step's outputs: --mode all or query, without --dry-run")
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus)            # (before fd 1 is redirected: the launched ranks inherit the real stdout)
     # ONE JSON line on stdout, nothing else: C libraries (RCCL prints a version banner) write to file descriptor 1 behind Python's
@@ -1270,14 +1319,17 @@ def main():
         args.dtype = "fp16x3"
     args.steps = defaults[0] if args.steps is None else args.steps
     args.warmup = defaults[1] if args.warmup is None else args.warmup
-    ctx = Ctx(args.gpus, one_rank_group=(args.mode in ("all", "train") and not args.dry_run and not args.no_ddp))
+    # the one-rank process group is for the training record: --mode train, or --mode all --full
+    train_record = args.mode == "train" or (args.mode == "all" and args.full)
+    # --dry-run: CPU + gloo even where GPUs are present (N ranks on a box with fewer GPUs)
+    ctx = Ctx(args.gpus, one_rank_group=(train_record and not args.dry_run and not args.no_ddp), use_gpu=not args.dry_run)
     if args.dry_run:
         # the distributed skeleton without the device work: used by the CPU test of the N > 1 launch path
         elapsed = ctx.timed(lambda: time.sleep(0.001 * (1 + ctx.rank)), args.steps, args.warmup)
         if ctx.rank == 0:
             line = base_line(args, ctx, "dry run", args.steps / elapsed, "steps/s", elapsed, True, "none",
                              {"workload": "dry run (no device work)"})
-            if args.mode == "all":      # the shape of the real line: the sub-records and their keys (tests/test_bench_launch.py)
+            if args.mode == "all" and args.full:    # the shape of the real line: the sub-records and their keys (tests/test_bench_launch.py)
                 sub = {"metric": "dry run", "value": 0.0, "unit": "-", "steps": 0, "warmup": 0, "ms_per_step": 0.0,
                        "higher_is_better": True, "dtype": "none", "config": {"workload": "dry run"},
                        "roofline": {"bound": "mfma", "achieved": 0.0, "peak": 1.0, "unit": "TFLOP/s", "frac": 0.0, "traffic": None},

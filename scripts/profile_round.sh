@@ -13,11 +13,11 @@ repo=$(pwd)
 out=$repo/gpurun_out
 mkdir -p $out
 export TMPDIR=/tmp
-timeout 900 python bench.py --steps 20 --warmup 5 > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 cd /tmp
 rm -rf /tmp/prof_$tag /tmp/profs_$tag
 timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_$tag -o $tag --output-format csv -- \
-    python $repo/bench.py --mode query --dtype $dt --steps 10 --warmup 3 --no-cpu-baseline > $out/${tag}_bench_under_rocprof.json 2> $out/${tag}_rocprof.err
+    python $repo/bench.py --mode query --full --dtype $dt --steps 10 --warmup 3 --no-cpu-baseline > $out/${tag}_bench_under_rocprof.json 2> $out/${tag}_rocprof.err
 f=$(find /tmp/prof_$tag -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $out/${tag}_kernel_stats.csv
 f=$(find /tmp/prof_$tag -name "*kernel_trace.csv" | head -1)
 [ -n "$f" ] && python $repo/scripts/prof_summary.py $f 60 > $out/${tag}_kernel_trace_summary.txt

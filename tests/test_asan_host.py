@@ -20,8 +20,9 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "chore_amd", "csrc")
 OUT = os.path.join(CSRC, "build_asan")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = ["--offload-arch=gfx950", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-fPIC", "-fsanitize=address", "-shared-libsan",
-         "-ffp-contract=off", "-Wno-unused-result", "-Wno-pass-failed"]
+# host code only: --cuda-host-only builds no device code, and -fno-gpu-sanitize keeps the sanitizer off any device pass
+FLAGS = ["--offload-arch=gfx950", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-fPIC", "-fsanitize=address", "-fno-gpu-sanitize",
+         "-shared-libsan", "-ffp-contract=off", "-Wno-unused-result", "-Wno-pass-failed"]
 
 
 def _asan_runtime():
@@ -57,7 +58,7 @@ def _build():
         for w in fat:
             f.write("const char %s[256] __attribute__((aligned(4096))) = {0};\n" % w)
     subprocess.check_call(["gcc", "-fPIC", "-c", stub, "-o", stub + ".o"])
-    subprocess.check_call([HIPCC, "-shared", "-fPIC", "-fsanitize=address", "-shared-libsan", "-o", lib] + objs + [stub + ".o"])
+    subprocess.check_call([HIPCC, "-shared", "-fPIC", "-fsanitize=address", "-fno-gpu-sanitize", "-shared-libsan", "-o", lib] + objs + [stub + ".o"])
     open(stamp, "w").write(h.hexdigest())
     return lib
 
@@ -128,7 +129,8 @@ def test_host_side_under_address_sanitizer(tmp_path):
     lib = _build()
     script = tmp_path / "child.py"
     script.write_text(CHILD)
-    env = dict(os.environ, LD_PRELOAD=_asan_runtime(), ASAN_OPTIONS="detect_leaks=0:abort_on_error=1:verify_asan_link_order=0",
+    preload = " ".join(p for p in (_asan_runtime(), os.environ.get("LD_PRELOAD")) if p)     # the runtime first; keep the caller's
+    env = dict(os.environ, LD_PRELOAD=preload, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1:verify_asan_link_order=0",
                HIP_VISIBLE_DEVICES="")
     out = subprocess.run([sys.executable, str(script), lib], capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0 and "asan host ok" in out.stdout, (out.stdout[-1000:], out.stderr[-3000:])

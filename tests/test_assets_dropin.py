@@ -1,20 +1,19 @@
 """CPU: the file readers behind FileAssets and the import aliases of chore_amd.dropin.
 
-Where /root/reference exists (the build container) the readers are checked against the reference's own asset files and
-the part labels its own loader returned (tests/golden/fit_init.npz); on the GPU box those checks are skipped -- the
-reference does not travel."""
+The readers are checked against the reference's own asset files, stored unchanged under tests/golden/assets/, and the part
+labels its own loader returned (tests/golden/fit_init.npz).  The aliases are checked from a stand-in CHORE checkout that
+the test writes: the files the import chain reads from a checkout (PATHS.yml, config/config_loader.py, a submodule that
+this package does not replace)."""
 import os
 import subprocess
 import sys
 
 import numpy as np
-import pytest
 
-from conftest import golden
+from conftest import GOLDEN, golden
 
-REF = "/root/reference"
+ASSETS = os.path.join(GOLDEN, "assets")
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-have_ref = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "assets")), reason="reference checkout not present")
 
 
 def test_ply_roundtrip(tmp_path):
@@ -85,10 +84,9 @@ def test_chumpy_free_smpl_reader(tmp_path):
         assert np.array_equal(b[k], a[k]), k
 
 
-@have_ref
 def test_file_assets_read_the_reference_asset_files():
     from chore_amd.recon.assets import FileAssets
-    fa = FileAssets(os.path.join(REF, "assets"))
+    fa = FileAssets(ASSETS)
     labels = fa.part_labels()
     assert np.array_equal(labels, golden("fit_init.npz")["part_labels"].astype(np.int32))   # = the reference loader's output
     b25, face, hand = fa.regressors()
@@ -96,14 +94,27 @@ def test_file_assets_read_the_reference_asset_files():
     assert np.allclose(b25.sum(1), 1.0, atol=1e-4)
     assert np.allclose(fa.mean_hand_pose(), golden("fit_init.npz")["mean_hand_pose"])
     import pickle
-    dat = pickle.load(open(os.path.join(REF, "assets/priors/body_prior.pkl"), "rb"))
+    dat = pickle.load(open(os.path.join(ASSETS, "priors", "body_prior.pkl"), "rb"))
     assert np.asarray(dat["mean"]).shape == (63,) and np.asarray(dat["precision"]).shape == (63, 63)
 
 
-@have_ref
-def test_dropin_aliases_resolve_from_a_reference_checkout():
-    """`from model import CHORE` etc. inside the reference tree resolve to this package; modules it does not replace
-    still come from the checkout (config.config_loader)"""
+def _standin_checkout(root):
+    """the files of a CHORE checkout that the drop-in import chain reads: PATHS.yml (at import time), config/, and a
+    recon submodule that this package does not replace"""
+    root.mkdir()
+    (root / "PATHS.yml").write_text('RECON_PATH: "recon_out"\nSMPL_ASSETS_ROOT: "assets"\n')
+    for pkg in ("config", "recon"):
+        (root / pkg).mkdir()
+    (root / "config" / "__init__.py").write_text("")
+    (root / "config" / "config_loader.py").write_text('"""stand-in for the checkout\'s config loader"""\n')
+    (root / "recon" / "opt_utils.py").write_text('"""stand-in for a checkout-only recon submodule"""\n')
+    return str(root)
+
+
+def test_dropin_aliases_resolve_from_a_reference_checkout(tmp_path):
+    """`from model import CHORE` etc. inside a CHORE checkout resolve to this package; modules it does not replace
+    still come from the checkout (config.config_loader, recon.opt_utils)"""
+    ref = _standin_checkout(tmp_path / "chore")
     code = ("import chore_amd.dropin as d; d.install(); "
             "from model import CHORE; from model.camera import KinectColorCamera; from recon.generator import Generator; "
             "from recon.recon_fit_base import ReconFitterBase, RECON_PATH, BEHAVE_PATH, SMPL_ASSETS_ROOT; "
@@ -113,11 +124,11 @@ def test_dropin_aliases_resolve_from_a_reference_checkout():
             "from lib_smpl.wrapper_pytorch import SMPLPyTorchWrapperBatch, SMPL_MODEL_ROOT, SMPL_ASSETS_ROOT as SA2; "
             "import inspect; assert RECON_PATH == RP2 and RECON_PATH is not None and SMPL_ASSETS_ROOT == 'assets' == SA2; "
             "assert inspect.signature(ReconFitterBase.__init__).parameters['outpath'].default == RECON_PATH; "
-            "import config.config_loader as cl; "
-            "print(CHORE.__module__, Generator.__module__, ReconFitterBase.__module__, cl.__file__)")
+            "import config.config_loader as cl; import recon.opt_utils as ou; "
+            "print(CHORE.__module__, Generator.__module__, ReconFitterBase.__module__, cl.__file__, ou.__file__)")
     env = dict(os.environ, PYTHONPATH=REPO)
-    out = subprocess.run([sys.executable, "-c", code], cwd=REF, capture_output=True, text=True, env=env, timeout=300)
+    out = subprocess.run([sys.executable, "-c", code], cwd=ref, capture_output=True, text=True, env=env, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     mods = out.stdout.split()
     assert mods[0] == "chore_amd.model.chore" and mods[1] == "chore_amd.recon.generator"
-    assert mods[2] == "chore_amd.recon.recon_fit_base" and mods[3].startswith(REF)
+    assert mods[2] == "chore_amd.recon.recon_fit_base" and mods[3].startswith(ref) and mods[4].startswith(ref)

@@ -51,11 +51,27 @@ def test_default_mode_schema_one_and_two_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     for world in (1, 2):
         out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", str(world), "--dry-run", "--steps", "2",
-                              "--warmup", "1"], capture_output=True, text=True, timeout=300, env=env, cwd=REPO)
+                              "--warmup", "1", "--full"], capture_output=True, text=True, timeout=300, env=env, cwd=REPO)
         assert out.returncode == 0, out.stderr[-2000:]
         lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
         assert len(lines) == 1, out.stdout
         _check_all_schema(json.loads(lines[0]), world)
+
+
+def test_plain_run_line_is_the_headline_only():
+    """without --full the default mode measures the headline and nothing else: the contract's keys, no sub-records"""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--dry-run", "--steps", "3",
+                          "--warmup", "1"], capture_output=True, text=True, timeout=300, env=env, cwd=REPO)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] >= 1.0
+    for k in ("fit", "train", "roofline", "cpu_baseline"):
+        assert k not in d, k
 
 
 def test_stdout_line_is_bounded():
