@@ -142,16 +142,18 @@ __global__ __launch_bounds__(1024) void lds_poison_kernel(unsigned pattern) {
     __syncthreads();
     if (lds_poison_mem[(threadIdx.x * 37) % (160 * 256)] != pattern) __builtin_trap();   // keeps the stores
 }
-void chore_lds_poison(hipStream_t s, const char* file, int line) {
+int chore_lds_poison(chore_handle* h, hipStream_t s, const char* file, int line) {
     static const unsigned pattern = (unsigned)strtoul(getenv("CHORE_LDS_POISON"), nullptr, 0) ? (unsigned)strtoul(getenv("CHORE_LDS_POISON"), nullptr, 0) : 0x7fc00000u;
     static const char* only = getenv("CHORE_LDS_POISON_FILE");
     static const int lo = getenv("CHORE_LDS_POISON_LINE_LO") ? atoi(getenv("CHORE_LDS_POISON_LINE_LO")) : 0;
     static const int hi = getenv("CHORE_LDS_POISON_LINE_HI") ? atoi(getenv("CHORE_LDS_POISON_LINE_HI")) : 1 << 30;
-    if (only && !strstr(file, only)) return;
-    if (line < lo || line > hi) return;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)lds_poison_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
-    hipLaunchKernelGGL(lds_poison_kernel, dim3(512), dim3(1024), 160 * 1024, s, pattern);      // one 160 KB workgroup per CU, twice over
+    if (only && !strstr(file, only)) return CHORE_OK;
+    if (line < lo || line > hi) return CHORE_OK;
+    const size_t smem = 160 * 1024;      // what lds_poison_kernel fills
+    // (not CHORE_LAUNCH: its launch check is what calls this function)
+    if (int rc = chore_lds_grant(h, (const void*)lds_poison_kernel, smem, file, line)) return rc;
+    hipLaunchKernelGGL(lds_poison_kernel, dim3(512), dim3(1024), smem, s, pattern);      // one 160 KB workgroup per CU, twice over
+    return CHORE_OK;
 }
 
 extern "C" int chore_debug_nan_counts(unsigned* out32) {

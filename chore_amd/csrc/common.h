@@ -14,15 +14,16 @@ struct chore_handle {
     std::string err;
     // cached encoder programs keyed by shape (see encoder.cpp)
     void* enc_cache = nullptr;
-    // one-off per-device setup that has been done for THIS handle's device (kernel attributes such as the dynamic LDS
-    // limit are per device): keyed by the address of a marker that is unique per call site / template instantiation
-    std::unordered_map<const void*, bool> once;
+    // dynamic LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize, a per-device attribute) that has been granted on THIS
+    // handle's device, in bytes, keyed by the kernel's address (chore_lds_grant); conv_pc.hip keeps its once-per-kernel
+    // occupancy check here too, under the address of a marker of its own
+    std::unordered_map<const void*, int> once;
     // training operators: a second stream (and fork / join events) for work that is independent inside one call, e.g. the
     // weight gradients of a ConvBlock beside its data-gradient chain (convblock.hip); created on first use
     hipStream_t side = nullptr;
     hipEvent_t side_ev[8] = {};
-    int cu_count = 0;          // hipDeviceAttributeMultiprocessorCount of `device`, read on first use (conv_rw.hip)
-    int lds_per_cu = 0;        // hipDeviceAttributeMaxSharedMemoryPerMultiprocessor of `device`, read on first use (conv_pc.hip)
+    int cu_count = 0;          // hipDeviceAttributeMultiprocessorCount of `device`, read on first use (chore_cu_count_cached)
+    int lds_per_cu = 0;        // hipDeviceAttributeMaxSharedMemoryPerMultiprocessor of `device`, read on first use (chore_lds_per_cu)
 };
 
 // every entry point runs with the handle's device current (a caller whose current device is another GPU -- e.g. the
@@ -43,7 +44,6 @@ struct ChoreDeviceGuard {
 #define CHORE_ENTER(h)                  \
     if (!(h)) return CHORE_EINVAL;      \
     ChoreDeviceGuard _chore_guard(h)
-#define CHORE_ONCE_FLAG(h) ([&]() -> bool& { static char _site; return (h)->once[(const void*)&_site]; }())
 
 #define CHORE_FAIL(h, code, ...)                         \
     do {                                                 \
@@ -72,20 +72,77 @@ inline bool chore_debug_sync() {
 // written gives results that depend on what ran before it -- on a GPU shared with another process that is another
 // process's data, and runs stop reproducing.  With the poison such a read shows up as a NaN (or a changed result) in a
 // single process.  CHORE_LDS_POISON_FILE / _LINE_LO / _LINE_HI restrict the poison to launch sites (bisection).
-extern "C" void chore_lds_poison(hipStream_t s, const char* file, int line);
+extern "C" int chore_lds_poison(chore_handle* h, hipStream_t s, const char* file, int line);
 inline bool chore_lds_poison_on() {
     static const bool v = getenv("CHORE_LDS_POISON") != nullptr;
     return v;
 }
+// `file` / `line` name the launch site (poison filter, CHORE_DEBUG_SYNC message, error text)
+inline int chore_launch_check(chore_handle* h, hipStream_t stream, const char* file, int line) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) CHORE_FAIL(h, CHORE_EHIP, "hipGetLastError() failed: %s (%s:%d)", hipGetErrorString(e), file, line);
+    if (chore_lds_poison_on())
+        if (int rc = chore_lds_poison(h, stream, file, line)) return rc;
+    if (chore_debug_sync()) {
+        fprintf(stderr, "[chore] launched at %s:%d\n", file, line);
+        e = hipStreamSynchronize(stream);
+        if (e != hipSuccess)
+            CHORE_FAIL(h, CHORE_EHIP, "hipStreamSynchronize(stream) failed: %s (%s:%d)", hipGetErrorString(e), file, line);
+    }
+    return CHORE_OK;
+}
 #define CHORE_LAUNCH_CHECK(h, stream)                                                         \
     do {                                                                                      \
-        CHORE_HIP_CHECK(h, hipGetLastError());                                                \
-        if (chore_lds_poison_on()) chore_lds_poison(stream, __FILE__, __LINE__);              \
-        if (chore_debug_sync()) {                                                             \
-            fprintf(stderr, "[chore] launched at %s:%d\n", __FILE__, __LINE__);               \
-            CHORE_HIP_CHECK(h, hipStreamSynchronize(stream));                                 \
-        }                                                                                     \
+        if (int _rc = chore_launch_check(h, stream, __FILE__, __LINE__)) return _rc;          \
     } while (0)
+
+// device attributes of the handle's device, read on first use (a failed query gives the MI355X's value)
+inline int chore_lds_per_cu(chore_handle* h) {
+    if (h->lds_per_cu <= 0 &&
+        (hipDeviceGetAttribute(&h->lds_per_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, h->device) != hipSuccess ||
+         h->lds_per_cu <= 0))
+        h->lds_per_cu = 160 * 1024;
+    return h->lds_per_cu;
+}
+inline int chore_cu_count_cached(chore_handle* h) {
+    if (h->cu_count <= 0 &&
+        (hipDeviceGetAttribute(&h->cu_count, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || h->cu_count <= 0))
+        h->cu_count = 256;
+    return h->cu_count;
+}
+
+// CHORE_LAUNCH(h, s, (kernel<...>), grid, block, lds, args...): the launch of a kernel that uses dynamic LDS (the others are
+// hipLaunchKernelGGL + CHORE_LAUNCH_CHECK).  `lds` is the request in bytes -- the one LDS number of a launch site -- or
+// chore_lds(request, limit) for a kernel whose request varies from launch to launch inside one instantiation: the limit
+// (the CU's LDS, or the largest request the kernel's shapes can make) is what the kernel is granted at its FIRST launch on
+// the handle, so that no later launch (one inside a captured graph, say) has to raise it; a request above it is refused.
+// From CHORE_LDS_ASK_FROM bytes on, the kernel's hipFuncAttributeMaxDynamicSharedMemorySize is raised before the launch; the
+// handle remembers what each kernel has been granted (chore_handle::once).  Returns CHORE_OK or the error; host code only.
+constexpr size_t CHORE_LDS_ASK_FROM = 64 * 1024;   // below this a kernel gets its dynamic LDS without asking
+struct chore_lds {
+    size_t smem, limit;
+    chore_lds(size_t smem_, size_t limit_ = 0) : smem(smem_), limit(limit_ ? limit_ : smem_) {}
+};
+inline int chore_lds_grant(chore_handle* h, const void* kernel, chore_lds lds, const char* file, int line) {
+    if (lds.smem > lds.limit)
+        CHORE_FAIL(h, CHORE_EINVAL, "launch asks for %zu bytes of LDS, the limit is %zu (%s:%d)", lds.smem, lds.limit, file, line);
+    if (lds.limit < CHORE_LDS_ASK_FROM) return CHORE_OK;
+    int& granted = h->once[kernel];
+    if ((size_t)granted >= lds.limit) return CHORE_OK;
+    hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds.limit);
+    if (e != hipSuccess)
+        CHORE_FAIL(h, CHORE_EHIP, "hipFuncSetAttribute(%zu bytes of LDS) failed: %s (%s:%d)", lds.limit, hipGetErrorString(e), file, line);
+    granted = (int)lds.limit;
+    return CHORE_OK;
+}
+template <typename... P, typename... A>
+inline int chore_launch(chore_handle* h, hipStream_t s, const char* file, int line, void (*kernel)(P...), dim3 grid, dim3 block,
+                        chore_lds lds, A&&... args) {
+    if (int rc = chore_lds_grant(h, (const void*)kernel, lds, file, line)) return rc;
+    hipLaunchKernelGGL(kernel, grid, block, lds.smem, s, args...);
+    return chore_launch_check(h, s, file, line);
+}
+#define CHORE_LAUNCH(h, s, ...) chore_launch(h, s, __FILE__, __LINE__, __VA_ARGS__)
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using f32x16 = __attribute__((ext_vector_type(16))) float;

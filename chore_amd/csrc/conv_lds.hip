@@ -481,18 +481,10 @@ __global__ __launch_bounds__(256, 2) void conv_lds_kernel(ConvArgs a) {
 template <typename T, int TAPS, int NT, int TPS_>
 int launch_t(chore_handle* h, const ConvArgs& a, hipStream_t s) {
     using G = Geo<TAPS, NT, TPS_, IS_X3<T>>;
-    const size_t smem = G::smem_bytes(a.in.C);
-    bool& attr = CHORE_ONCE_FLAG(h);
-    if (!attr) {
-        CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)conv_lds_kernel<T, TAPS, NT, TPS_>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-        attr = true;
-    }
+    const chore_lds smem(G::smem_bytes(a.in.C), chore_lds_per_cu(h));      // grows with the input channels
     const int tiles = ((a.W + TW - 1) / TW) * ((a.H + TH - 1) / TH);
     dim3 grid(tiles * (a.Cout / NT) * a.B);
-    hipLaunchKernelGGL((conv_lds_kernel<T, TAPS, NT, TPS_>), grid, dim3(256), smem, s, a);
-    CHORE_LAUNCH_CHECK(h, s);
-    return CHORE_OK;
+    return CHORE_LAUNCH(h, s, (conv_lds_kernel<T, TAPS, NT, TPS_>), grid, dim3(256), smem, a);
 }
 
 template <typename T, int TAPS>

@@ -654,11 +654,8 @@ template <typename T, int TAPS, int TH, int NT, int TPS, int NSLOT, bool GN, boo
 int launch_mw_t(chore_handle* h, const ConvArgs& a, hipStream_t s) {
     using G = MGeo<TAPS, TH, NT, TPS, NSLOT, IS_X3<T>, std::is_same<T, bf16_t>::value ? 1 : 2>;
     size_t smem = G::smem_bytes(a.in.C);
-    if (h->lds_per_cu <= 0) {
-        CHORE_HIP_CHECK(h, hipDeviceGetAttribute(&h->lds_per_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, h->device));
-        if (h->lds_per_cu <= 0) h->lds_per_cu = 160 * 1024;
-    }
-    if (smem > (size_t)h->lds_per_cu) CHORE_FAIL(h, CHORE_EINVAL, "conv_mw: %zu bytes of LDS, the CU has %d", smem, h->lds_per_cu);
+    const size_t lds_cu = chore_lds_per_cu(h);
+    if (smem > lds_cu) CHORE_FAIL(h, CHORE_EINVAL, "conv_mw: %zu bytes of LDS, the CU has %zu", smem, lds_cu);
     // The workgroup takes ALL of the CU's LDS, whatever its tiling needs: no other workgroup that uses LDS -- of this kernel or of any
     // other -- shares the CU with it.  Round 6 measured why (scripts/pipe_stress.py, profiles/r06_pipe_stress.txt): with the small
     // tilings (2 x 32 x 64: 64 KB) requesting what they need, or half the CU + 1 KB like conv_pc_kernel, a fit that runs on another
@@ -667,19 +664,11 @@ int launch_mw_t(chore_handle* h, const ConvArgs& a, hipStream_t s) {
     // (8 waves x 256 registers).  What exactly goes wrong when LDS-using workgroups of other kernels sit beside these four
     // 1-wave-per-SIMD MFMA waves is NOT understood; the cost of the exclusion is nil inside the kernel.
     static const size_t lds_min_env = getenv("CHORE_CONV_MW_LDS_MIN") ? (size_t)atol(getenv("CHORE_CONV_MW_LDS_MIN")) : 0;   // experiments
-    const size_t lds_min = lds_min_env ? lds_min_env : (size_t)h->lds_per_cu;
+    const size_t lds_min = lds_min_env ? lds_min_env : lds_cu;
     if (smem < lds_min) smem = lds_min;
-    bool& attr = CHORE_ONCE_FLAG(h);
-    if (!attr) {
-        CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)conv_mw_kernel<T, TAPS, TH, NT, TPS, NSLOT, GN, SC>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_per_cu));
-        attr = true;
-    }
     const int tiles = ((a.W + PTW - 1) / PTW) * ((a.H + TH - 1) / TH);
     dim3 grid(tiles * (a.Cout / NT) * a.B);
-    hipLaunchKernelGGL((conv_mw_kernel<T, TAPS, TH, NT, TPS, NSLOT, GN, SC>), grid, dim3(MWT), smem, s, a);
-    CHORE_LAUNCH_CHECK(h, s);
-    return CHORE_OK;
+    return CHORE_LAUNCH(h, s, (conv_mw_kernel<T, TAPS, TH, NT, TPS, NSLOT, GN, SC>), grid, dim3(MWT), chore_lds(smem, lds_cu), a);
 }
 
 }  // namespace

@@ -658,30 +658,25 @@ int launch_pc_t(chore_handle* h, const ConvArgs& a, hipStream_t s) {
     // The request is derived from the device's LDS per CU (not a constant), and the first launch of every tiling ASKS the
     // runtime how many of these workgroups a CU would hold: anything but one is refused (a later change that shrinks the
     // request, or a part with more LDS per CU, would bring the starvation back silently otherwise -- ADVICE round 3).
-    if (h->lds_per_cu <= 0) {
-        CHORE_HIP_CHECK(h, hipDeviceGetAttribute(&h->lds_per_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, h->device));
-        if (h->lds_per_cu <= 0) h->lds_per_cu = 160 * 1024;
-    }
-    const int lds_cu = h->lds_per_cu;
+    const int lds_cu = chore_lds_per_cu(h);
     if (smem > (size_t)lds_cu) CHORE_FAIL(h, CHORE_EINVAL, "conv_pc: %zu bytes of LDS, the CU has %d", smem, lds_cu);
     if (smem < (size_t)lds_cu / 2 + 1024) smem = (size_t)lds_cu / 2 + 1024;
-    bool& attr = CHORE_ONCE_FLAG(h);
-    if (!attr) {
-        CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)conv_pc_kernel<T, TAPS, TH, NT, TPS, NSLOT, SC>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, lds_cu));
+    const auto kernel = conv_pc_kernel<T, TAPS, TH, NT, TPS, NSLOT, SC>;
+    const chore_lds lds(smem, lds_cu);
+    static char occupancy_site;        // one per tiling (template instantiation)
+    int& occupancy_checked = h->once[&occupancy_site];
+    if (!occupancy_checked) {
+        if (int rc = chore_lds_grant(h, (const void*)kernel, lds, __FILE__, __LINE__)) return rc;
         int per_cu = 0;
-        CHORE_HIP_CHECK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)conv_pc_kernel<T, TAPS, TH, NT, TPS, NSLOT, SC>,
-                                                                        512, smem));
+        CHORE_HIP_CHECK(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kernel, 512, smem));
         if (per_cu != 1)
             CHORE_FAIL(h, CHORE_EINVAL, "conv_pc: %d workgroups per CU with %zu bytes of LDS -- the hand-over by polling needs exactly one",
                        per_cu, smem);
-        attr = true;
+        occupancy_checked = 1;
     }
     const int tiles = ((a.W + PTW - 1) / PTW) * ((a.H + TH - 1) / TH);
     dim3 grid(tiles * (a.Cout / NT) * a.B);
-    hipLaunchKernelGGL((conv_pc_kernel<T, TAPS, TH, NT, TPS, NSLOT, SC>), grid, dim3(512), smem, s, a);
-    CHORE_LAUNCH_CHECK(h, s);
-    return CHORE_OK;
+    return CHORE_LAUNCH(h, s, kernel, grid, dim3(512), lds, a);
 }
 
 }  // namespace

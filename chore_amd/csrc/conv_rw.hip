@@ -343,28 +343,18 @@ template <typename T, int KC, int WN, bool RES, bool SC = false>
 int launch_rw_t(chore_handle* h, const ConvArgs& a, hipStream_t s) {
     using G = RGeo<KC, WN, IS_X3<T> ? 2 : 1>;
     const size_t smem = G::smem_bytes();
-    bool& attr = CHORE_ONCE_FLAG(h);
-    if (!attr) {
-        CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)conv_rw_kernel<T, KC, WN, RES, SC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr = true;
-    }
-    if (h->cu_count <= 0) {
-        CHORE_HIP_CHECK(h, hipDeviceGetAttribute(&h->cu_count, hipDeviceAttributeMultiprocessorCount, h->device));
-        if (h->cu_count <= 0) h->cu_count = 256;
-    }
     // one persistent workgroup per CU: every image's blocks are dealt to cu / B workgroups in contiguous runs
     const int nblk = (a.H * a.W + G::MPX - 1) / G::MPX;
     // ... on THREE QUARTERS of the CUs (CHORE_CONV_RW_CUS=n: n): these layers are bound by HBM, 192 workgroups move the bytes as fast
     // as 256 (one step at a time 4.99 -> 4.86 ms) and the other step in flight gets a quarter of the chip for its MFMA-bound
     // convolutions meanwhile (two in flight 4.01 -> 3.87 ms; 224 / 160 / 128: 3.91 / 3.86 / 3.90; profiles/r06_conv_fill.txt)
     static const int cus_env = getenv("CHORE_CONV_RW_CUS") ? atoi(getenv("CHORE_CONV_RW_CUS")) : 0;
-    int wpi = (cus_env > 0 ? cus_env : (h->cu_count * 3) / 4) / a.B;
+    int wpi = (cus_env > 0 ? cus_env : (chore_cu_count_cached(h) * 3) / 4) / a.B;
     if (wpi < 1) wpi = 1;
     if (wpi > nblk) wpi = nblk;
     const int bpw = (nblk + wpi - 1) / wpi;
     wpi = (nblk + bpw - 1) / bpw;
-    hipLaunchKernelGGL((conv_rw_kernel<T, KC, WN, RES, SC>), dim3((unsigned)(wpi * a.B)), dim3(512), smem, s, a, bpw, wpi);
-    CHORE_LAUNCH_CHECK(h, s);
+    if (int rc = CHORE_LAUNCH(h, s, (conv_rw_kernel<T, KC, WN, RES, SC>), dim3((unsigned)(wpi * a.B)), dim3(512), smem, a, bpw, wpi)) return rc;
 #if CHORE_RW_STAMPS
     {
         static int shown = 0;

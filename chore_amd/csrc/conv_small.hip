@@ -358,16 +358,8 @@ int launch_small_t(chore_handle* h, const ConvArgs& a, hipStream_t s) {
     if constexpr (G::smem > 160 * 1024) {
         CHORE_FAIL(h, CHORE_EINVAL, "conv_small: %d rows x %d channels do not fit the LDS", ROWS, CIN);
     } else {
-        bool& attr = CHORE_ONCE_FLAG(h);
-        if (!attr) {
-            CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)conv_small_kernel<T, CIN, ROWS>,
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::smem));
-            attr = true;
-        }
         const unsigned grid = (unsigned)((size_t)a.B * (a.H / ROWS) * (a.W / 32) * (a.Cout / 32));
-        hipLaunchKernelGGL((conv_small_kernel<T, CIN, ROWS>), dim3(grid), dim3(256), G::smem, s, a);
-        CHORE_LAUNCH_CHECK(h, s);
-        return CHORE_OK;
+        return CHORE_LAUNCH(h, s, (conv_small_kernel<T, CIN, ROWS>), dim3(grid), dim3(256), G::smem, a);
     }
 }
 

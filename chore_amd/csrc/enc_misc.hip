@@ -109,33 +109,10 @@ int launch_stem(chore_handle* h, int dtype, const float* images, int B, int Cin,
     if (Cin > STEM_MAXC) CHORE_FAIL(h, CHORE_EINVAL, "stem: Cin > %d", STEM_MAXC);
     const int OH = H / 2, OW = W / 2;
     dim3 grid((OW + STEM_T - 1) / STEM_T, (OH + STEM_T - 1) / STEM_T, B);
-    const size_t smem = (size_t)Cin * STEM_P * STEM_P * sizeof(float);
-    bool* attr[3] = {&CHORE_ONCE_FLAG(h), &CHORE_ONCE_FLAG(h), &CHORE_ONCE_FLAG(h)};
-    if (dtype == CHORE_F16) {
-        if (!*attr[2]) {
-            CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)stem_kernel<h16_t>,
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            *attr[2] = true;
-        }
-        hipLaunchKernelGGL(stem_kernel<h16_t>, grid, dim3(256), smem, s, images, B, Cin, H, W, wk, bias, (h16_t*)out);
-    } else if (dtype == CHORE_F32) {
-        if (!*attr[0]) {
-            CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)stem_kernel<float>,
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            *attr[0] = true;
-        }
-        hipLaunchKernelGGL(stem_kernel<float>, grid, dim3(256), smem, s, images, B, Cin, H, W, wk, bias, (float*)out);
-    } else {
-        if (!*attr[1]) {
-            CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)stem_kernel<bf16_t>,
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            *attr[1] = true;
-        }
-        hipLaunchKernelGGL(stem_kernel<bf16_t>, grid, dim3(256), smem, s, images, B, Cin, H, W, wk, bias,
-                           (bf16_t*)out);
-    }
-    CHORE_LAUNCH_CHECK(h, s);
-    return CHORE_OK;
+    const chore_lds smem((size_t)Cin * STEM_P * STEM_P * sizeof(float), chore_lds_per_cu(h));      // grows with Cin
+    if (dtype == CHORE_F16) return CHORE_LAUNCH(h, s, stem_kernel<h16_t>, grid, dim3(256), smem, images, B, Cin, H, W, wk, bias, (h16_t*)out);
+    if (dtype == CHORE_F32) return CHORE_LAUNCH(h, s, stem_kernel<float>, grid, dim3(256), smem, images, B, Cin, H, W, wk, bias, (float*)out);
+    return CHORE_LAUNCH(h, s, stem_kernel<bf16_t>, grid, dim3(256), smem, images, B, Cin, H, W, wk, bias, (bf16_t*)out);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -321,20 +298,11 @@ int launch_stem_x3(chore_handle* h, const float* images, int B, int Cin, int H, 
                    hipStream_t s) {
     const int OH = H / 2, OW = W / 2;
     dim3 grid((OW + SX_TW - 1) / SX_TW, (OH + STEM_T - 1) / STEM_T, B);
-    const size_t smem = (size_t)Cin * STEM_P * SX_PS2 * sizeof(float);
-    bool& attr = CHORE_ONCE_FLAG(h);
-    if (!attr) {       // 53 KB for five channels
-        (void)hipFuncSetAttribute((const void*)stem_x3_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        (void)hipFuncSetAttribute((const void*)stem_x3_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        (void)hipFuncSetAttribute((const void*)stem_x3_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-        attr = true;
-    }
-    if (Cin == 5) hipLaunchKernelGGL(stem_x3_kernel<5>, grid, dim3(256), smem, s, images, B, H, W, (const u32x4*)wfr, bias, out);
-    else if (Cin == 4) hipLaunchKernelGGL(stem_x3_kernel<4>, grid, dim3(256), smem, s, images, B, H, W, (const u32x4*)wfr, bias, out);
-    else if (Cin == 3) hipLaunchKernelGGL(stem_x3_kernel<3>, grid, dim3(256), smem, s, images, B, H, W, (const u32x4*)wfr, bias, out);
-    else CHORE_FAIL(h, CHORE_EINVAL, "stem (fp16 x 3): Cin = %d not instantiated", Cin);
-    CHORE_LAUNCH_CHECK(h, s);
-    return CHORE_OK;
+    const size_t smem = (size_t)Cin * STEM_P * SX_PS2 * sizeof(float);       // 53 KB for five channels
+    if (Cin == 5) return CHORE_LAUNCH(h, s, stem_x3_kernel<5>, grid, dim3(256), smem, images, B, H, W, (const u32x4*)wfr, bias, out);
+    if (Cin == 4) return CHORE_LAUNCH(h, s, stem_x3_kernel<4>, grid, dim3(256), smem, images, B, H, W, (const u32x4*)wfr, bias, out);
+    if (Cin == 3) return CHORE_LAUNCH(h, s, stem_x3_kernel<3>, grid, dim3(256), smem, images, B, H, W, (const u32x4*)wfr, bias, out);
+    CHORE_FAIL(h, CHORE_EINVAL, "stem (fp16 x 3): Cin = %d not instantiated", Cin);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -673,15 +641,7 @@ template <typename T, int C, typename Op>
 static int launch_map_c(chore_handle* h, const Op& op, const View& y, int B, int OH, int OW, GroupStat* st,
                         hipStream_t s) {
     dim3 grid(((OH + MAP_T - 1) / MAP_T) * ((OW + Op::TW - 1) / Op::TW), B, C / Op::CT);
-    bool& attr = CHORE_ONCE_FLAG(h);   // per instantiation
-    if (!attr && Op::SMEM > 32 * 1024) {
-        CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)map_stats_kernel<T, C, Op>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)Op::SMEM));
-        attr = true;
-    }
-    hipLaunchKernelGGL((map_stats_kernel<T, C, Op>), grid, dim3(256), Op::SMEM, s, op, (T*)y.p, y.cs, y.co, OH, OW, st);
-    CHORE_LAUNCH_CHECK(h, s);
-    return CHORE_OK;
+    return CHORE_LAUNCH(h, s, (map_stats_kernel<T, C, Op>), grid, dim3(256), Op::SMEM, op, (T*)y.p, y.cs, y.co, OH, OW, st);
 }
 
 template <typename T>

@@ -437,23 +437,9 @@ int chore_heads_wgrad(chore_handle* h, const void* staging, int B, int N, const 
     a.part_b4 = a.part4 + HW_PART4;
     a.out = grads; a.accumulate = accumulate;
     const size_t smem = (size_t)2 * HW_KT * 256 * sizeof(float);
-    bool& attr = CHORE_ONCE_FLAG(h);
-    if (!attr) {
-        CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)heads_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr = true;
-    }
-    if (heads_x3) {
-        bool& attrx = CHORE_ONCE_FLAG(h);
-        if (!attrx) {
-            CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)heads_wgrad_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)HX_SMEM));
-            attrx = true;
-        }
-        hipLaunchKernelGGL(heads_wgrad_x3_kernel, dim3(HW_S, HW_TILES), dim3(256), HX_SMEM, s, a);
-    } else {
-        hipLaunchKernelGGL(heads_wgrad_kernel, dim3(HW_S, HW_TILES), dim3(256), smem, s, a);
-    }
-    CHORE_LAUNCH_CHECK(h, s);
+    if (int rc = heads_x3 ? CHORE_LAUNCH(h, s, heads_wgrad_x3_kernel, dim3(HW_S, HW_TILES), dim3(256), HX_SMEM, a)
+                          : CHORE_LAUNCH(h, s, heads_wgrad_kernel, dim3(HW_S, HW_TILES), dim3(256), smem, a))
+        return rc;
     hipLaunchKernelGGL(heads_out_wgrad_kernel, dim3(HW_S4, HEAD_NUM), dim3(256), 0, s, a);
     CHORE_LAUNCH_CHECK(h, s);
     const size_t n = (size_t)HW_TILES * 128 * 128 + (size_t)HW_TILES * 128 + (size_t)HEAD_NUM * HW_OMAX * 128 + HEAD_NUM * 16;

@@ -462,18 +462,10 @@ __global__ __launch_bounds__(NW * 64, 1) void query_bwd_f32_kernel(QueryArgs a) 
 
 template <typename T, bool TRAIN, int NCB, bool X3 = false>
 static int launch_query_bwd_n(chore_handle* h, const QueryArgs& a, hipStream_t s) {
-    bool& attr_set = CHORE_ONCE_FLAG(h);
     constexpr int PTS = 32 * NCB;
     const size_t smem = sizeof(QueryBwdSmemT<PTS>);
-    if (!attr_set) {
-        CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)query_bwd_f32_kernel<T, TRAIN, NCB, false, 4, X3>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_set = true;
-    }
     dim3 grid((a.N + PTS - 1) / PTS, a.B);
-    hipLaunchKernelGGL((query_bwd_f32_kernel<T, TRAIN, NCB, false, 4, X3>), grid, dim3(256), smem, s, a);
-    CHORE_LAUNCH_CHECK(h, s);
-    return CHORE_OK;
+    return CHORE_LAUNCH(h, s, (query_bwd_f32_kernel<T, TRAIN, NCB, false, 4, X3>), grid, dim3(256), smem, a);
 }
 
 bool query_small_tiles(int B, int N);   // query_fwd.hip: 32-point tiles when 64-point tiles would not fill the CUs
@@ -491,18 +483,10 @@ static bool query_one_head() { static const bool off = getenv("CHORE_QUERY_NO_ON
 
 template <typename T, int NCB, bool SURF = true, bool ONE = false>
 static int launch_query_surf_n(chore_handle* h, const QueryArgs& a, hipStream_t s) {
-    bool& attr_set = CHORE_ONCE_FLAG(h);
     constexpr int PTS = 32 * NCB;
     const size_t smem = sizeof(QueryBwdSmemT<PTS>);
-    if (!attr_set) {
-        CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)query_bwd_f32_kernel<T, false, NCB, false, 4, true, SURF, ONE>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_set = true;
-    }
     dim3 grid((a.N + PTS - 1) / PTS, a.B);
-    hipLaunchKernelGGL((query_bwd_f32_kernel<T, false, NCB, false, 4, true, SURF, ONE>), grid, dim3(256), smem, s, a);
-    CHORE_LAUNCH_CHECK(h, s);
-    return CHORE_OK;
+    return CHORE_LAUNCH(h, s, (query_bwd_f32_kernel<T, false, NCB, false, 4, true, SURF, ONE>), grid, dim3(256), smem, a);
 }
 template <typename T>
 static int launch_query_surf_t(chore_handle* h, const QueryArgs& a, hipStream_t s) {
@@ -520,17 +504,9 @@ int launch_query_surface_step(chore_handle* h, int dtype, const QueryArgs& a, hi
 // the eight-wave variants (64-point tile, two waves per head)
 template <typename T, bool TRAIN, bool STAGED, bool X3 = false>
 static int launch_query_bwd_w8(chore_handle* h, const QueryArgs& a, hipStream_t s) {
-    bool& attr_set = CHORE_ONCE_FLAG(h);
     const size_t smem = sizeof(QueryBwdSmemT<64>);
-    if (!attr_set) {
-        CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)query_bwd_f32_kernel<T, TRAIN, 1, STAGED, 8, X3>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_set = true;
-    }
     dim3 grid((a.N + 63) / 64, a.B);
-    hipLaunchKernelGGL((query_bwd_f32_kernel<T, TRAIN, 1, STAGED, 8, X3>), grid, dim3(512), smem, s, a);
-    CHORE_LAUNCH_CHECK(h, s);
-    return CHORE_OK;
+    return CHORE_LAUNCH(h, s, (query_bwd_f32_kernel<T, TRAIN, 1, STAGED, 8, X3>), grid, dim3(512), smem, a);
 }
 
 static bool query_w4() { static const bool v = getenv("CHORE_QUERY_W4") != nullptr; return v; }   // A/B switch
@@ -571,17 +547,9 @@ static int launch_query_bwd_staged_x3(chore_handle* h, const QueryArgs& a, hipSt
 
 template <typename T>
 static int launch_query_bwd_staged_t(chore_handle* h, const QueryArgs& a, hipStream_t s) {
-    bool& attr_set = CHORE_ONCE_FLAG(h);
     const size_t smem = sizeof(QueryBwdSmemT<64>);
-    if (!attr_set) {
-        CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)query_bwd_f32_kernel<T, true, 2, true>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_set = true;
-    }
     dim3 grid((a.N + 63) / 64, a.B);
-    hipLaunchKernelGGL((query_bwd_f32_kernel<T, true, 2, true>), grid, dim3(256), smem, s, a);
-    CHORE_LAUNCH_CHECK(h, s);
-    return CHORE_OK;
+    return CHORE_LAUNCH(h, s, (query_bwd_f32_kernel<T, true, 2, true>), grid, dim3(256), smem, a);
 }
 
 int launch_query_bwd_f32(chore_handle* h, const QueryArgs& a, hipStream_t s) {

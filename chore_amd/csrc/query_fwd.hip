@@ -481,18 +481,10 @@ __global__ __launch_bounds__(512, 1) void query_fwd_x3_split_kernel(QueryArgs a)
 
 template <typename T, int NCB>
 static int launch_query_fwd_split(chore_handle* h, const QueryArgs& a, hipStream_t s) {
-    bool& attr_set = CHORE_ONCE_FLAG(h);
     constexpr int PTS = 32 * NCB;
     const size_t smem = sizeof(QuerySplitSmemT<PTS>);
-    if (!attr_set) {
-        CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)query_fwd_x3_split_kernel<T, NCB>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_set = true;
-    }
     dim3 grid((a.N + PTS - 1) / PTS, a.B);
-    hipLaunchKernelGGL((query_fwd_x3_split_kernel<T, NCB>), grid, dim3(512), smem, s, a);
-    CHORE_LAUNCH_CHECK(h, s);
-    return CHORE_OK;
+    return CHORE_LAUNCH(h, s, (query_fwd_x3_split_kernel<T, NCB>), grid, dim3(512), smem, a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -531,17 +523,9 @@ __global__ __launch_bounds__(256) void sample_features_kernel(QueryArgs a, float
 
 template <typename T>
 static int launch_sample_features_t(chore_handle* h, const QueryArgs& a, float* features, float* nxy, hipStream_t s) {
-    bool& attr_set = CHORE_ONCE_FLAG(h);
     const size_t smem = sizeof(QueryFwdSmem);
-    if (!attr_set) {
-        CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)sample_features_kernel<T>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_set = true;
-    }
     dim3 grid((a.N + QT_PTS - 1) / QT_PTS, a.B);
-    hipLaunchKernelGGL(sample_features_kernel<T>, grid, dim3(256), smem, s, a, features, nxy);
-    CHORE_LAUNCH_CHECK(h, s);
-    return CHORE_OK;
+    return CHORE_LAUNCH(h, s, sample_features_kernel<T>, grid, dim3(256), smem, a, features, nxy);
 }
 int launch_sample_features(chore_handle* h, int dtype, const QueryArgs& a, float* features, float* nxy, hipStream_t s) {
     return dtype == CHORE_F32 ? launch_sample_features_t<float>(h, a, features, nxy, s)
@@ -735,18 +719,10 @@ size_t heads_arena_bytes() { return QX_ARENA_BYTES; }
 
 template <typename T, int NCB, bool X3 = false>
 static int launch_query_fwd_n(chore_handle* h, const QueryArgs& a, hipStream_t s) {
-    bool& attr_set = CHORE_ONCE_FLAG(h);
     constexpr int PTS = 32 * NCB;
     const size_t smem = sizeof(QueryFwdSmemT<PTS>);
-    if (!attr_set) {
-        CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)query_fwd_f32_kernel<T, NCB, false, X3>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_set = true;
-    }
     dim3 grid((a.N + PTS - 1) / PTS, a.B);
-    hipLaunchKernelGGL((query_fwd_f32_kernel<T, NCB, false, X3>), grid, dim3(256), smem, s, a);
-    CHORE_LAUNCH_CHECK(h, s);
-    return CHORE_OK;
+    return CHORE_LAUNCH(h, s, (query_fwd_f32_kernel<T, NCB, false, X3>), grid, dim3(256), smem, a);
 }
 
 // 64-point tiles unless they would leave CUs without a workgroup
@@ -754,17 +730,9 @@ bool query_small_tiles(int B, int N) { return (size_t)B * ((N + QT_PTS - 1) / QT
 
 template <typename T, bool X3 = false>
 static int launch_query_fwd_w8(chore_handle* h, const QueryArgs& a, hipStream_t s) {
-    bool& attr_set = CHORE_ONCE_FLAG(h);
     const size_t smem = sizeof(QueryFwdSmemT<64>);
-    if (!attr_set) {
-        CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)query_fwd_f32_w8_kernel<T, false, X3>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_set = true;
-    }
     dim3 grid((a.N + 63) / 64, a.B);
-    hipLaunchKernelGGL((query_fwd_f32_w8_kernel<T, false, X3>), grid, dim3(512), smem, s, a);
-    CHORE_LAUNCH_CHECK(h, s);
-    return CHORE_OK;
+    return CHORE_LAUNCH(h, s, (query_fwd_f32_w8_kernel<T, false, X3>), grid, dim3(512), smem, a);
 }
 
 template <typename T, bool X3 = false>
@@ -787,33 +755,17 @@ static int launch_query_fwd_t(chore_handle* h, const QueryArgs& a, hipStream_t s
 
 template <typename T, bool X3 = false>
 static int launch_query_fwd_train_w8(chore_handle* h, const QueryArgs& a, hipStream_t s) {
-    bool& attr_set = CHORE_ONCE_FLAG(h);
     const size_t smem = sizeof(QueryFwdSmemT<64>) + 8 * 32 * ST_LD * sizeof(float);     // + the waves' store-transpose tiles
-    if (!attr_set) {
-        CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)query_fwd_f32_w8_kernel<T, true, X3>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_set = true;
-    }
     dim3 grid((a.N + 63) / 64, a.B);
-    hipLaunchKernelGGL((query_fwd_f32_w8_kernel<T, true, X3>), grid, dim3(512), smem, s, a);
-    CHORE_LAUNCH_CHECK(h, s);
-    return CHORE_OK;
+    return CHORE_LAUNCH(h, s, (query_fwd_f32_w8_kernel<T, true, X3>), grid, dim3(512), smem, a);
 }
 
 template <typename T, bool X3 = false>
 static int launch_query_fwd_train_t(chore_handle* h, const QueryArgs& a, hipStream_t s) {
     if (!getenv("CHORE_QUERY_W4")) return launch_query_fwd_train_w8<T, X3>(h, a, s);
-    bool& attr_set = CHORE_ONCE_FLAG(h);
     const size_t smem = sizeof(QueryFwdSmemT<64>);
-    if (!attr_set) {
-        CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)query_fwd_f32_kernel<T, 2, true, X3>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        attr_set = true;
-    }
     dim3 grid((a.N + 63) / 64, a.B);
-    hipLaunchKernelGGL((query_fwd_f32_kernel<T, 2, true, X3>), grid, dim3(256), smem, s, a);
-    CHORE_LAUNCH_CHECK(h, s);
-    return CHORE_OK;
+    return CHORE_LAUNCH(h, s, (query_fwd_f32_kernel<T, 2, true, X3>), grid, dim3(256), smem, a);
 }
 // x3: the heads on the fp16 matrix cores with split operands (either map type)
 int launch_query_fwd_train(chore_handle* h, int dtype, const QueryArgs& a, hipStream_t s, int x3) {

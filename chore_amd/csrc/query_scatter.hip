@@ -354,12 +354,7 @@ __global__ __launch_bounds__(1024) void query_perm_kernel(QueryArgs a, int nb, i
 
 int launch_scatter_features(chore_handle* h, const QueryArgs& a, const float* dX, float* dfeat, float* dtmpx,
                             int accumulate, hipStream_t s) {
-    bool& attr = CHORE_ONCE_FLAG(h);
-    if (!attr) {
-        CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)scatter_csr_kernel<FEAT_C, 8, 8>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 8 * FEAT_C * 4));
-        attr = true;
-    }
+    const auto csr_feat = scatter_csr_kernel<FEAT_C, 8, 8>;      // 64 KB of LDS
     if (!a.tSort) CHORE_FAIL(h, CHORE_EINVAL, "scatter_features: the staging buffer has no sort region");
     if (a.N <= 0) return CHORE_OK;
     // windows of the map's tiles: <= 16 x 16 (the sort's count table and offset tables hold 256 tiles); one sort + one walk per
@@ -374,8 +369,8 @@ int launch_scatter_features(chore_handle* h, const QueryArgs& a, const float* dX
             for (int wx = 0; wx < txn; wx += win) {
                 const TileWin tw{wx, wy, txn - wx < win ? txn - wx : win, tyn - wy < win ? tyn - wy : win};
                 hipLaunchKernelGGL((scatter_bin_kernel<8>), dim3(G, a.B), dim3(64), 0, s, a, a.FH, a.FW, sort, tw);
-                hipLaunchKernelGGL((scatter_csr_kernel<FEAT_C, 8, 8>), dim3(tw.wtx, tw.wty, a.B), dim3(256), 8 * 8 * FEAT_C * 4,
-                                   s, a, dX, 0, a.FH, a.FW, dfeat, accumulate, (const int*)sort, tw);
+                if (int rc = CHORE_LAUNCH(h, s, csr_feat, dim3(tw.wtx, tw.wty, a.B), dim3(256), 8 * 8 * FEAT_C * 4,
+                                          a, dX, 0, a.FH, a.FW, dfeat, accumulate, (const int*)sort, tw)) return rc;
             }
     }
     if (dtmpx) {
@@ -388,11 +383,10 @@ int launch_scatter_features(chore_handle* h, const QueryArgs& a, const float* dX
                 // 8 x 8-texel workgroups inside the 16 x 16 tiles: two per tile edge, clipped to the map
                 const int bx = (a.TW + 7) / 8 - 2 * wx, by = (a.TH + 7) / 8 - 2 * wy;
                 const int gx = 2 * tw.wtx < bx ? 2 * tw.wtx : bx, gy = 2 * tw.wty < by ? 2 * tw.wty : by;
-                hipLaunchKernelGGL((scatter_csr_kernel<TMPX_C, 16, 8>), dim3(gx, gy, a.B), dim3(256), 8 * 8 * TMPX_C * 4,
-                                   s, a, dX, FEAT_C + 3, a.TH, a.TW, dtmpx, accumulate, (const int*)sort, tw);
+                if (int rc = CHORE_LAUNCH(h, s, (scatter_csr_kernel<TMPX_C, 16, 8>), dim3(gx, gy, a.B), dim3(256), 8 * 8 * TMPX_C * 4,
+                                          a, dX, FEAT_C + 3, a.TH, a.TW, dtmpx, accumulate, (const int*)sort, tw)) return rc;
             }
     }
-    CHORE_LAUNCH_CHECK(h, s);
     return CHORE_OK;
 }
 
@@ -403,15 +397,9 @@ bool query_sort_covers(const QueryArgs& a) {
 int launch_query_sort(chore_handle* h, const QueryArgs& a, int* work, hipStream_t s) {
     const int CH = scatter_chunk(a.N), G = (a.N + CH - 1) / CH;
     const int nb = ((a.FW + 7) / 8) * ((a.FH + 7) / 8);
-    const size_t smem = ((size_t)G * SCATTER_OFF_STRIDE + nb + 4 + (size_t)(nb + 1) * G) * sizeof(int);
-    bool& attr = CHORE_ONCE_FLAG(h);
-    if (!attr) {
-        CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)query_perm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)((64 * SCATTER_OFF_STRIDE + 264 + 257 * 64) * sizeof(int))));
-        attr = true;
-    }
+    // grows with the point count and the map: granted once for the largest covered shape (64 chunks, 256 tiles)
+    const chore_lds smem(((size_t)G * SCATTER_OFF_STRIDE + nb + 4 + (size_t)(nb + 1) * G) * sizeof(int),
+                         (64 * SCATTER_OFF_STRIDE + 264 + 257 * 64) * sizeof(int));
     hipLaunchKernelGGL((query_bin_kernel<8>), dim3(G, a.B), dim3(64), 0, s, a, a.FH, a.FW, work);
-    hipLaunchKernelGGL(query_perm_kernel, dim3(8, a.B), dim3(1024), smem, s, a, nb, work);
-    CHORE_LAUNCH_CHECK(h, s);
-    return CHORE_OK;
+    return CHORE_LAUNCH(h, s, query_perm_kernel, dim3(8, a.B), dim3(1024), smem, a, nb, work);
 }

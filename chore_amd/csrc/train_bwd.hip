@@ -1351,6 +1351,17 @@ int conv2d_bwd_weight_impl(chore_handle* h, int dtype, int taps, const void* x, 
     a.xs = Cin; a.ys = dy_stride; a.npix = (long long)B * H * W;
     a.part = (float*)workspace;
     int ct = 32;
+    // after a layer's partial sums are launched (rc: that launch's result): the sum over the shares now, or, with `defer`, a
+    // record of it for launch_wgrad_finish_multi
+    auto finish = [&](int rc) -> int {
+        if (rc) return rc;
+        if (defer) { defer->j[defer->n++] = {a.part, a.part_bias, dw, dbias, a.S, Cout, Cin, taps, ct}; return CHORE_OK; }
+        const size_t n = (size_t)Cout * Cin * taps;
+        hipLaunchKernelGGL(wgrad_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.part, a.part_bias, a.S, Cout,
+                           Cin, taps, dw, dbias, ct);
+        CHORE_LAUNCH_CHECK(h, s);
+        return CHORE_OK;
+    };
     if (wgrad_use64(dtype, taps, Cin, Cout)) {
         ct = 64;
         const bool x3 = dtype == CHORE_F16X3;
@@ -1368,81 +1379,24 @@ int conv2d_bwd_weight_impl(chore_handle* h, int dtype, int taps, const void* x, 
             const int np128 = (Cout / 128) * (Cin / 128);
             a.part_bias = dbias ? a.part + (size_t)a.S * np128 * 16384 : nullptr;
             const size_t sm128 = (size_t)2 * 4 * W128_PX * W128_PITCH;
-            bool& attr128 = CHORE_ONCE_FLAG(h);
-            if (!attr128) {
-                CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)wgrad128_x3_pc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm128));
-                attr128 = true;
-            }
-            hipLaunchKernelGGL(wgrad128_x3_pc_kernel, dim3(a.S * np128), dim3(512), sm128, s, a);
-            CHORE_LAUNCH_CHECK(h, s);
-            if (defer) { defer->j[defer->n++] = {a.part, a.part_bias, dw, dbias, a.S, Cout, Cin, taps, ct}; return CHORE_OK; }
-            const size_t n = (size_t)Cout * Cin * taps;
-            hipLaunchKernelGGL(wgrad_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.part, a.part_bias, a.S, Cout,
-                               Cin, taps, dw, dbias, ct);
-            CHORE_LAUNCH_CHECK(h, s);
-            return CHORE_OK;
+            return finish(CHORE_LAUNCH(h, s, wgrad128_x3_pc_kernel, dim3(a.S * np128), dim3(512), sm128, a));
         }
         if (x3 && use_pc) {
             a.S = wgrad64_x3_pc_shares(B, H, W, Cin, Cout);
             a.part_bias = dbias ? a.part + (size_t)a.S * npairs * taps * 4096 : nullptr;
             const size_t arows = taps == 9 ? (size_t)(WP_TH + 2) * PW : (size_t)WP_TH * TW;
             const size_t smp = (size_t)2 * 2 * (arows + WP_TH * TW) * W64_PITCH;
-            bool& attrp = CHORE_ONCE_FLAG(h);
-            if (!attrp) {
-                CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)wgrad64_x3_pc_kernel<9>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       (int)((size_t)4 * ((WP_TH + 2) * PW + WP_TH * TW) * W64_PITCH)));
-                CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)wgrad64_x3_pc_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       (int)((size_t)4 * (2 * WP_TH * TW) * W64_PITCH)));
-                attrp = true;
-            }
-            if (taps == 9) hipLaunchKernelGGL(wgrad64_x3_pc_kernel<9>, dim3(a.S * npairs), dim3(512), smp, s, a);
-            else hipLaunchKernelGGL(wgrad64_x3_pc_kernel<1>, dim3(a.S * npairs), dim3(512), smp, s, a);
-            CHORE_LAUNCH_CHECK(h, s);
-            if (defer) { defer->j[defer->n++] = {a.part, a.part_bias, dw, dbias, a.S, Cout, Cin, taps, ct}; return CHORE_OK; }
-            const size_t n = (size_t)Cout * Cin * taps;
-            hipLaunchKernelGGL(wgrad_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.part, a.part_bias, a.S, Cout,
-                               Cin, taps, dw, dbias, ct);
-            CHORE_LAUNCH_CHECK(h, s);
-            return CHORE_OK;
+            return finish(taps == 9 ? CHORE_LAUNCH(h, s, wgrad64_x3_pc_kernel<9>, dim3(a.S * npairs), dim3(512), smp, a)
+                                    : CHORE_LAUNCH(h, s, wgrad64_x3_pc_kernel<1>, dim3(a.S * npairs), dim3(512), smp, a));
         }
         if (x3) {
             const size_t smx = (size_t)2 * ((taps == 9 ? (WX_TH + 2) * PW : WX_TH * TW) + WX_TH * TW) * W64_PITCH + 64 * 2 * sizeof(float);
-            bool& attrx = CHORE_ONCE_FLAG(h);
-            if (!attrx) {
-                CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)wgrad64_x3_kernel<9>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       (int)((size_t)2 * ((WX_TH + 2) * PW + WX_TH * TW) * W64_PITCH + 512)));
-                CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)wgrad64_x3_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       (int)((size_t)2 * (2 * WX_TH * TW) * W64_PITCH + 512)));
-                attrx = true;
-            }
-            if (taps == 9) hipLaunchKernelGGL(wgrad64_x3_kernel<9>, dim3(a.S * npairs), dim3(256), smx, s, a);
-            else hipLaunchKernelGGL(wgrad64_x3_kernel<1>, dim3(a.S * npairs), dim3(256), smx, s, a);
-            CHORE_LAUNCH_CHECK(h, s);
-            if (defer) { defer->j[defer->n++] = {a.part, a.part_bias, dw, dbias, a.S, Cout, Cin, taps, ct}; return CHORE_OK; }
-            const size_t n = (size_t)Cout * Cin * taps;
-            hipLaunchKernelGGL(wgrad_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.part, a.part_bias, a.S, Cout,
-                               Cin, taps, dw, dbias, ct);
-            CHORE_LAUNCH_CHECK(h, s);
-            return CHORE_OK;
+            return finish(taps == 9 ? CHORE_LAUNCH(h, s, wgrad64_x3_kernel<9>, dim3(a.S * npairs), dim3(256), smx, a)
+                                    : CHORE_LAUNCH(h, s, wgrad64_x3_kernel<1>, dim3(a.S * npairs), dim3(256), smx, a));
         }
         const size_t smem64 = (size_t)((taps == 9 ? PH * PW : TH * TW) + TH * TW) * W64_PITCH + 64 * 2 * sizeof(float);
-        bool& attr64 = CHORE_ONCE_FLAG(h);
-        if (!attr64) {
-            CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)wgrad64_kernel<9>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)((size_t)(PH * PW + TH * TW) * W64_PITCH + 512)));
-            CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)wgrad64_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)((size_t)(2 * TH * TW) * W64_PITCH + 512)));
-            attr64 = true;
-        }
-        if (taps == 9) hipLaunchKernelGGL(wgrad64_kernel<9>, dim3(a.S * npairs), dim3(256), smem64, s, a);
-        else hipLaunchKernelGGL(wgrad64_kernel<1>, dim3(a.S * npairs), dim3(256), smem64, s, a);
-        CHORE_LAUNCH_CHECK(h, s);
-        if (defer) { defer->j[defer->n++] = {a.part, a.part_bias, dw, dbias, a.S, Cout, Cin, taps, ct}; return CHORE_OK; }
-        const size_t n = (size_t)Cout * Cin * taps;
-        hipLaunchKernelGGL(wgrad_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.part, a.part_bias, a.S, Cout,
-                           Cin, taps, dw, dbias, ct);
-        CHORE_LAUNCH_CHECK(h, s);
-        return CHORE_OK;
+        return finish(taps == 9 ? CHORE_LAUNCH(h, s, wgrad64_kernel<9>, dim3(a.S * npairs), dim3(256), smem64, a)
+                                : CHORE_LAUNCH(h, s, wgrad64_kernel<1>, dim3(a.S * npairs), dim3(256), smem64, a));
     }
     if (dtype == CHORE_F16X3) dtype = CHORE_F32;      // channel counts below 64 (the 256^2 block): the exact fp32 matrix-core kernel
     a.S = wgrad_shares(B, H, W, Cin, Cout);
@@ -1452,25 +1406,11 @@ int conv2d_bwd_weight_impl(chore_handle* h, int dtype, int taps, const void* x, 
     size_t smem = (size_t)(arows + TH * TW) * CT32 * es + 256;
     if (smem < 4 * 1024 * sizeof(float)) smem = 4 * 1024 * sizeof(float);
     dim3 grid(Cout / 32, Cin / 32, a.S);
-#define LAUNCH_WG(T, TP)                                                                                              \
-    do {                                                                                                              \
-        bool& attr = CHORE_ONCE_FLAG(h);                                                                                     \
-        if (!attr) {                                                                                                  \
-            CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)wgrad_kernel<T, TP>,                                 \
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));          \
-            attr = true;                                                                                              \
-        }                                                                                                             \
-        hipLaunchKernelGGL((wgrad_kernel<T, TP>), grid, dim3(256), smem, s, a);                                      \
-    } while (0)
-    if (dtype == CHORE_F32) { if (taps == 9) LAUNCH_WG(float, 9); else LAUNCH_WG(float, 1); }
-    else { if (taps == 9) LAUNCH_WG(bf16_t, 9); else LAUNCH_WG(bf16_t, 1); }
-#undef LAUNCH_WG
-    if (defer) { CHORE_LAUNCH_CHECK(h, s); defer->j[defer->n++] = {a.part, a.part_bias, dw, dbias, a.S, Cout, Cin, taps, ct}; return CHORE_OK; }
-    const size_t n = (size_t)Cout * Cin * taps;
-    hipLaunchKernelGGL(wgrad_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.part, a.part_bias, a.S, Cout,
-                       Cin, taps, dw, dbias, ct);
-    CHORE_LAUNCH_CHECK(h, s);
-    return CHORE_OK;
+    if (dtype == CHORE_F32)
+        return finish(taps == 9 ? CHORE_LAUNCH(h, s, (wgrad_kernel<float, 9>), grid, dim3(256), smem, a)
+                                : CHORE_LAUNCH(h, s, (wgrad_kernel<float, 1>), grid, dim3(256), smem, a));
+    return finish(taps == 9 ? CHORE_LAUNCH(h, s, (wgrad_kernel<bf16_t, 9>), grid, dim3(256), smem, a)
+                            : CHORE_LAUNCH(h, s, (wgrad_kernel<bf16_t, 1>), grid, dim3(256), smem, a));
 }
 
 int launch_wgrad_finish_multi(chore_handle* h, const WgradFinishJobs& jobs, hipStream_t s) {
@@ -1521,14 +1461,8 @@ int chore_gemm_tn_f32(chore_handle* h, const float* A, int lda, const float* B, 
     a.S = wgrad_shares(1, a.H, a.W, N, M);
     a.part = (float*)workspace;
     a.part_bias = nullptr;
-    size_t smem = (size_t)(2 * TH * TW) * CT32 * 4 + 256;
-    bool& attr = CHORE_ONCE_FLAG(h);
-    if (!attr) {
-        CHORE_HIP_CHECK(h, hipFuncSetAttribute((const void*)wgrad_kernel<float, 1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               96 * 1024));
-        attr = true;
-    }
-    hipLaunchKernelGGL((wgrad_kernel<float, 1>), dim3(M / 32, N / 32, a.S), dim3(256), smem, s, a);
+    const size_t smem = (size_t)(2 * TH * TW) * CT32 * 4 + 256;
+    if (int rc = CHORE_LAUNCH(h, s, (wgrad_kernel<float, 1>), dim3(M / 32, N / 32, a.S), dim3(256), smem, a)) return rc;
     const size_t n = (size_t)M * N;
     hipLaunchKernelGGL(wgrad_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.part, nullptr, a.S, M, N, 1, C,
                        nullptr, 32);

@@ -29,7 +29,7 @@ static float frand(unsigned& s) {
     return ((s >> 8) & 0xffff) / 32768.0f - 1.0f;
 }
 
-extern "C" void chore_lds_poison(hipStream_t, const char*, int) {}   // capi.hip is not linked into the probe
+extern "C" int chore_lds_poison(chore_handle*, hipStream_t, const char*, int) { return 0; }   // capi.hip is not linked into the probe
 
 int main(int argc, char** argv) {
     const int dtype = argc > 1 ? atoi(argv[1]) : CHORE_F16X3;
