@@ -19,19 +19,9 @@
 //     in flight; the per-vertex sums are combined by a fixed butterfly, so the result is deterministic.
 // Degenerate edges (a zero denominator makes the crossing coordinate non-finite) are skipped, like the
 // restatement in oracle/silhouette.py does; with real-valued vertices they have measure zero.
-#include "common.h"
+#include "raster_common.h"     // TriSetup, tri_backside, tri_setup, raster_hit: shared with render.hip
 
 namespace {
-
-struct TriSetup {            // per (image, triangle)
-    float f[9];              // projected vertices: x0 y0 z0 x1 y1 z1 x2 y2 z2 (normalised [-1,1] + depth)
-    float inv[9];            // pixel-space inverse (barycentric weights = inv * (xi, yi, 1))
-    int x0, x1, y0, y1;      // inclusive pixel bounding box, x0 > x1 if the triangle is culled
-};
-
-__device__ __forceinline__ bool tri_backside(const float* f) {
-    return __fmul_rn(f[7] - f[1], f[3] - f[0]) < __fmul_rn(f[4] - f[1], f[6] - f[0]);
-}
 
 __global__ void sil_setup_kernel(const float* __restrict__ faces, int n /*B*F*/, int size, TriSetup* __restrict__ ts) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -39,33 +29,7 @@ __global__ void sil_setup_kernel(const float* __restrict__ faces, int n /*B*F*/,
     TriSetup t;
 #pragma unroll
     for (int k = 0; k < 9; ++k) t.f[k] = faces[(size_t)i * 9 + k];
-    t.x0 = 1; t.x1 = 0; t.y0 = 1; t.y1 = 0;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) t.inv[k] = 0.f;
-    if (!tri_backside(t.f)) {
-        const float S = (float)size;
-        float p[3][2];
-#pragma unroll
-        for (int v = 0; v < 3; ++v)
-#pragma unroll
-            for (int d = 0; d < 2; ++d) p[v][d] = 0.5f * ((t.f[3 * v + d] * S + S) - 1.0f);
-        const float den = (p[2][0] * (p[0][1] - p[1][1]) + p[0][0] * (p[1][1] - p[2][1])) + p[1][0] * (p[2][1] - p[0][1]);
-        const float m[9] = {p[1][1] - p[2][1], p[2][0] - p[1][0], p[1][0] * p[2][1] - p[2][0] * p[1][1],
-                            p[2][1] - p[0][1], p[0][0] - p[2][0], p[2][0] * p[0][1] - p[0][0] * p[2][1],
-                            p[0][1] - p[1][1], p[1][0] - p[0][0], p[0][0] * p[1][1] - p[1][0] * p[0][1]};
-#pragma unroll
-        for (int k = 0; k < 9; ++k) t.inv[k] = m[k] / den;
-        // conservative box: pixel centres inside the triangle lie within [min, max] of the vertex pixel coordinates;
-        // one pixel of slack covers the rounding of the normalised-coordinate inside test
-        const float xmin = fminf(fminf(p[0][0], p[1][0]), p[2][0]), xmax = fmaxf(fmaxf(p[0][0], p[1][0]), p[2][0]);
-        const float ymin = fminf(fminf(p[0][1], p[1][1]), p[2][1]), ymax = fmaxf(fmaxf(p[0][1], p[1][1]), p[2][1]);
-        if (xmin == xmin && ymin == ymin && xmax == xmax && ymax == ymax) {   // not NaN
-            t.x0 = (int)fmaxf(floorf(xmin) - 1.f, 0.f);
-            t.y0 = (int)fmaxf(floorf(ymin) - 1.f, 0.f);
-            t.x1 = (int)fminf(ceilf(xmax) + 1.f, S - 1.f);
-            t.y1 = (int)fminf(ceilf(ymax) + 1.f, S - 1.f);
-        }
-    }
+    tri_setup(t, size);
     ts[i] = t;
 }
 
@@ -111,24 +75,8 @@ __global__ __launch_bounds__(256) void sil_fwd_kernel(const TriSetup* __restrict
         if (inside) {
             for (int h = 0; h < nh; ++h) {
                 const int j = hits[h];
-                const float* f = tri[j].f;
-                if (__fmul_rn(yp - f[1], f[3] - f[0]) < __fmul_rn(xp - f[0], f[4] - f[1]) ||
-                    __fmul_rn(yp - f[4], f[6] - f[3]) < __fmul_rn(xp - f[3], f[7] - f[4]) ||
-                    __fmul_rn(yp - f[7], f[0] - f[6]) < __fmul_rn(xp - f[6], f[1] - f[7]))
-                    continue;
-                const float* m = tri[j].inv;
-                float w[3], ws = 0.f;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    float v = (m[3 * k] * xf + m[3 * k + 1] * yf) + m[3 * k + 2];
-                    v = fminf(fmaxf(v, 0.f), 1.f);     // NaN -> 0 like CUDA's fmax/fmin
-                    w[k] = v;
-                }
-                ws = (w[0] + w[1]) + w[2];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) w[k] = w[k] / ws;
-                const float zp = 1.0f / ((w[0] / f[2] + w[1] / f[5]) + w[2] / f[8]);
-                if (zp <= near || far <= zp) continue;
+                float w[3], zp;
+                if (!raster_hit(tri[j].f, tri[j].inv, xp, yp, xf, yf, near, far, w, zp)) continue;
                 if (zp < depth) { depth = zp; best = c0 + j; }
             }
         }

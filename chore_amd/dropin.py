@@ -12,11 +12,13 @@
     recon, recon.generator, recon.recon_fit_base, recon.recon_fit_behave, recon.recon_fit_coco, recon.obj_pose_roi,
     recon.eval.chamfer_distance, recon.eval.pose_utils
     lib_smpl, lib_smpl.const, lib_smpl.wrapper_pytorch, lib_smpl.smpl_generator
+    utils, utils.render_utils, neural_renderer, neural_renderer.renderer
 
 resolve to chore_amd's classes, while every submodule this package does not replace (recon.opt_utils, recon.bbox,
-lib_smpl.body_landmark, data.*, behave.*, config.*, trainer.*, utils.*) is still found in the reference checkout: the
-alias packages get the checkout's directories appended to their search path.  Nothing is copied and no file of the
-reference is modified.
+lib_smpl.body_landmark, utils.dist_utils, data.*, behave.*, config.*, trainer.*) is still found in the reference checkout:
+the alias packages get the checkout's directories appended to their search path.  Nothing is copied and no file of the
+reference is modified.  With `utils.render_utils` and `neural_renderer` aliased, demo.py's rendering half (the overlay and the
+side view) runs on the HIP rasteriser; its `cv2` (JPEG reading / writing, a CPU library) is the user's own.
 """
 import importlib
 import os
@@ -41,6 +43,10 @@ ALIASES = {
     "lib_smpl.const": "chore_amd.lib_smpl.const",
     "lib_smpl.wrapper_pytorch": "chore_amd.lib_smpl.wrapper_pytorch",
     "lib_smpl.smpl_generator": "chore_amd.lib_smpl.smpl_generator",
+    "utils": "chore_amd.utils",
+    "utils.render_utils": "chore_amd.utils.render_utils",
+    "neural_renderer": "chore_amd.render",
+    "neural_renderer.renderer": "chore_amd.render.renderer",
 }
 
 

@@ -1,0 +1,236 @@
+"""Colour / depth / coverage renderer for looking at fitted meshes, on the HIP rasteriser (chore_render_fwd).
+
+Counterpart of the vendored neural_renderer as the reference's visualisation uses it
+(external/neural_renderer/neural_renderer/ of a CHORE checkout: renderer.py:11-63,237-283 Renderer / render, lighting.py,
+look_at.py, perspective.py, get_points_from_angles.py, rasterize.py:267-348 rasterize_rgbad).  The camera and light
+steps are vertex- and face-sized tensor expressions and run wherever their inputs live; rasterisation, texture sampling,
+the vertical flip and the 2x2 anti-aliasing average are one call into libchore_hip.so and need device tensors.
+
+Forward only: the reference renders for visualisation and never differentiates through `Renderer.render`; inputs that
+require grad are detached.
+
+Kept quirks of the reference: `light_direction` is used un-normalised; face normals are
+normalize(cross(v0 - v1, v2 - v1), eps=1e-5), dividing by max(norm, eps); lighting sees the world vertices, before the camera.
+One deliberate difference: the reference multiplies the whole texture cube of every face by its light before sampling
+(lighting.py:55-56); here the per-face light (B,F,3) goes to the kernel, which multiplies the blended texel -- the same
+product up to fp32 rounding, without materialising lit textures.
+"""
+import ctypes
+import math
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .. import _lib
+from ..recon.obj_pose_roi import projection, vertices_to_faces
+
+DEFAULT_NEAR, DEFAULT_FAR, DEFAULT_EPS = 0.1, 100.0, 1e-3      # renderer.py:16,63
+
+
+def get_points_from_angles(distance, elevation, azimuth, degrees=True):
+    """get_points_from_angles.py:6-24"""
+    if isinstance(distance, (float, int)):
+        if degrees:
+            elevation, azimuth = math.radians(elevation), math.radians(azimuth)
+        return (distance * math.cos(elevation) * math.sin(azimuth), distance * math.sin(elevation),
+                -distance * math.cos(elevation) * math.cos(azimuth))
+    if degrees:
+        elevation, azimuth = math.pi / 180. * elevation, math.pi / 180. * azimuth
+    return torch.stack([distance * torch.cos(elevation) * torch.sin(azimuth), distance * torch.sin(elevation),
+                        -distance * torch.cos(elevation) * torch.cos(azimuth)]).transpose(1, 0)
+
+
+def _vec(x, device, batch):
+    t = torch.as_tensor(np.asarray(x) if isinstance(x, (list, tuple)) else x, dtype=torch.float32).to(device)
+    return t[None, :].repeat(batch, 1) if t.dim() == 1 else t
+
+
+def look_at(vertices, eye, at=(0, 0, 0), up=(0, 1, 0)):
+    """look_at.py:6-62: camera at `eye` looking at `at`"""
+    if vertices.dim() != 3:
+        raise ValueError("vertices Tensor should have 3 dimensions")
+    B, dev = vertices.shape[0], vertices.device
+    eye, at, up = _vec(eye, dev, B), _vec(at, dev, B), _vec(up, dev, B)
+    z_axis = F.normalize(at - eye, eps=1e-5)
+    x_axis = F.normalize(torch.cross(up, z_axis, dim=1), eps=1e-5)
+    y_axis = F.normalize(torch.cross(z_axis, x_axis, dim=1), eps=1e-5)
+    r = torch.stack((x_axis, y_axis, z_axis), dim=1)
+    return torch.matmul(vertices - eye[:, None, :], r.transpose(1, 2))
+
+
+def perspective(vertices, angle=30.):
+    """perspective.py:6-21"""
+    if vertices.dim() != 3:
+        raise ValueError("vertices Tensor should have 3 dimensions")
+    width = torch.tan(torch.tensor(angle / 180 * math.pi, dtype=torch.float32, device=vertices.device))
+    z = vertices[:, :, 2]
+    return torch.stack((vertices[:, :, 0] / z / width, vertices[:, :, 1] / z / width, z), dim=2)
+
+
+def face_light(faces, intensity_ambient=0.5, intensity_directional=0.5, color_ambient=(1, 1, 1),
+               color_directional=(1, 1, 1), direction=(0, 1, 0)):
+    """the light of lighting.py:32-52 per face: faces (B,F,3,3) world-space triangles -> (B,F,3)"""
+    bs, nf = faces.shape[:2]
+    dev = faces.device
+
+    def vec(x):
+        t = torch.as_tensor(np.asarray(x) if isinstance(x, (list, tuple)) else x).float().to(dev)
+        return t[None, :] if t.dim() == 1 else t
+    color_ambient, color_directional, direction = vec(color_ambient), vec(color_directional), vec(direction)
+    light = torch.zeros(bs, nf, 3, dtype=torch.float32, device=dev)
+    if intensity_ambient != 0:
+        light = light + intensity_ambient * color_ambient[:, None, :]
+    if intensity_directional != 0:
+        f = faces.reshape(bs * nf, 3, 3)
+        normals = F.normalize(torch.cross(f[:, 0] - f[:, 1], f[:, 2] - f[:, 1], dim=1), eps=1e-5).reshape(bs, nf, 3)
+        cos = F.relu(torch.sum(normals * direction[:, None, :], dim=2))
+        light = light + intensity_directional * (color_directional[:, None, :] * cos[:, :, None])
+    return light
+
+
+def lighting(faces, textures, intensity_ambient=0.5, intensity_directional=0.5, color_ambient=(1, 1, 1),
+             color_directional=(1, 1, 1), direction=(0, 1, 0)):
+    """lighting.py:5-57 with its signature: the lit textures (a new tensor; the reference multiplies in place).  The
+    renderer does not call this -- it hands `face_light` to the kernel; kept for comparison and for callers of the reference"""
+    light = face_light(faces, intensity_ambient, intensity_directional, color_ambient, color_directional, direction)
+    return textures * light[:, :, None, None, None, :]
+
+
+def rasterize_rgbad(faces, textures, light=None, image_size=256, anti_aliasing=True, near=DEFAULT_NEAR, far=DEFAULT_FAR,
+                    eps=DEFAULT_EPS, background_color=(0, 0, 0), return_index=False):
+    """rasterize.py:267-348 in one call: faces (B,F,3,3) projected triangles, textures (B,F,ts,ts,ts,3), light (B,F,3) or None
+    -> dict(rgb (B,3,S,S), depth (B,S,S), alpha (B,S,S)[, face_index (B,S*ssaa,S*ssaa) int32, rows not flipped])"""
+    if not faces.is_cuda:
+        raise RuntimeError("chore_amd needs device tensors (no CPU path)")
+    dev = faces.device
+    h = _lib.handle(dev.index or 0)
+    tri = faces.detach().float().contiguous()
+    tex = textures.detach().to(dev).float().contiguous()
+    B, Fn = tri.shape[:2]
+    ts = tex.shape[2]
+    if tuple(tri.shape) != (B, Fn, 3, 3) or tuple(tex.shape) != (B, Fn, ts, ts, ts, 3):
+        raise ValueError("faces (B,F,3,3) and textures (B,F,ts,ts,ts,3) expected, got %s and %s" % (tuple(tri.shape), tuple(tex.shape)))
+    lt = None
+    if light is not None:
+        lt = light.detach().to(dev).float().contiguous()
+        if tuple(lt.shape) != (B, Fn, 3):
+            raise ValueError("light (B,F,3) expected")
+    ssaa, S = (2 if anti_aliasing else 1), int(image_size)
+    nbytes = _lib.lib.chore_render_workspace_bytes(B, Fn, S, ssaa)
+    if nbytes == 0:
+        raise ValueError("unsupported render shape B=%d F=%d image_size=%d ssaa=%d" % (B, Fn, S, ssaa))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    rgb = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
+    depth = torch.empty(B, S, S, dtype=torch.float32, device=dev)
+    alpha = torch.empty(B, S, S, dtype=torch.float32, device=dev)
+    fim = torch.empty(B, S * ssaa, S * ssaa, dtype=torch.int32, device=dev) if return_index else None
+    bg = (ctypes.c_float * 3)(*[float(c) for c in background_color])
+    _lib.check(_lib.lib.chore_render_fwd(h, tri.data_ptr(), tex.data_ptr(), lt.data_ptr() if lt is not None else None, B, Fn, ts,
+                                         S, ssaa, float(near), float(far), float(eps), bg, rgb.data_ptr(), depth.data_ptr(),
+                                         alpha.data_ptr(), fim.data_ptr() if return_index else None, ws.data_ptr(),
+                                         torch.cuda.current_stream(dev).cuda_stream), h, "chore_render_fwd")
+    out = {"rgb": rgb, "depth": depth, "alpha": alpha}
+    if return_index:
+        out["face_index"] = fim
+    return out
+
+
+class Renderer(nn.Module):
+    """neural_renderer.Renderer (renderer.py:11-63): same constructor arguments and attributes.  K / R / t may live on any
+    device; they are moved to the vertices' device when rendering."""
+
+    def __init__(self, image_size=256, anti_aliasing=True, background_color=[0, 0, 0], fill_back=True,
+                 camera_mode="projection", K=None, R=None, t=None, dist_coeffs=None, orig_size=1024, perspective=True,
+                 viewing_angle=30, camera_direction=[0, 0, 1], near=0.1, far=100, light_intensity_ambient=0.5,
+                 light_intensity_directional=0.5, light_color_ambient=[1, 1, 1], light_color_directional=[1, 1, 1],
+                 light_direction=[0, 1, 0]):
+        super().__init__()
+        self.image_size = image_size
+        self.anti_aliasing = anti_aliasing
+        self.background_color = background_color
+        self.fill_back = fill_back
+        self.camera_mode = camera_mode
+        if camera_mode == "projection":
+            as_t = lambda x: torch.as_tensor(x, dtype=torch.float32) if isinstance(x, np.ndarray) else x    # noqa: E731
+            self.K, self.R, self.t = as_t(K), as_t(R), as_t(t)
+            self.dist_coeffs = torch.zeros(1, 5) if dist_coeffs is None else dist_coeffs
+            self.orig_size = orig_size
+        elif camera_mode in ("look", "look_at"):
+            self.perspective = perspective
+            self.viewing_angle = viewing_angle
+            self.eye = [0, 0, -(1. / math.tan(math.radians(self.viewing_angle)) + 1)]
+            self.camera_direction = [0, 0, 1]
+        else:
+            raise ValueError("Camera mode has to be one of projection, look or look_at")
+        self.near = near
+        self.far = far
+        self.light_intensity_ambient = light_intensity_ambient
+        self.light_intensity_directional = light_intensity_directional
+        self.light_color_ambient = light_color_ambient
+        self.light_color_directional = light_color_directional
+        self.light_direction = light_direction
+        self.rasterizer_eps = 1e-3
+
+    def forward(self, vertices, faces, textures=None, mode=None, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
+        if mode is None:
+            return self.render(vertices, faces, textures, K, R, t, dist_coeffs, orig_size)
+        if mode == "rgb":
+            return self.render_rgb(vertices, faces, textures, K, R, t, dist_coeffs, orig_size)
+        if mode == "silhouettes":
+            return self.render_silhouettes(vertices, faces, K, R, t, dist_coeffs, orig_size)
+        if mode == "depth":
+            return self.render_depth(vertices, faces, K, R, t, dist_coeffs, orig_size)
+        raise ValueError("mode should be one of None, 'rgb', 'silhouettes' or 'depth'")
+
+    def transform(self, vertices, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
+        """world vertices (B,V,3) -> [u, v in [-1,1], depth] under the camera mode (renderer.py:254-276)"""
+        if self.camera_mode == "look_at":
+            vertices = look_at(vertices, self.eye)
+            return perspective(vertices, angle=self.viewing_angle) if self.perspective else vertices
+        if self.camera_mode == "look":
+            raise NotImplementedError("camera mode 'look' is not provided")
+        dev = vertices.device
+        K = self.K if K is None else K
+        R = self.R if R is None else R
+        t = self.t if t is None else t
+        dist_coeffs = self.dist_coeffs if dist_coeffs is None else dist_coeffs
+        orig_size = self.orig_size if orig_size is None else orig_size
+        on = lambda x: torch.as_tensor(x, dtype=torch.float32).to(dev)     # noqa: E731
+        return projection(vertices, on(K), on(R), on(t), on(dist_coeffs), orig_size)
+
+    def _rasterize(self, vertices, faces, textures, cam, return_index=False):
+        vertices = vertices.detach().float()
+        faces = faces.detach()
+        light = None
+        if textures is None:        # coverage / depth only: one white texel cube per face
+            textures = torch.ones(faces.shape[0], faces.shape[1], 2, 2, 2, 3, dtype=torch.float32, device=vertices.device)
+            lit = False
+        else:
+            textures = textures.detach().to(vertices.device).float()
+            lit = True
+        if self.fill_back:
+            faces = torch.cat((faces, faces.flip(-1)), dim=1)
+            textures = torch.cat((textures, textures.permute((0, 1, 4, 3, 2, 5))), dim=1)
+        if lit:
+            light = face_light(vertices_to_faces(vertices, faces), self.light_intensity_ambient,
+                               self.light_intensity_directional, self.light_color_ambient, self.light_color_directional,
+                               self.light_direction)
+        tri = vertices_to_faces(self.transform(vertices, *cam), faces)
+        return rasterize_rgbad(tri, textures, light, self.image_size, self.anti_aliasing, self.near, self.far,
+                               self.rasterizer_eps, self.background_color, return_index=return_index)
+
+    def render(self, vertices, faces, textures, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
+        """-> (rgb (B,3,S,S), depth (B,S,S), alpha (B,S,S))   (renderer.py:237-283); inputs are detached"""
+        out = self._rasterize(vertices, faces, textures, (K, R, t, dist_coeffs, orig_size))
+        return out["rgb"], out["depth"], out["alpha"]
+
+    def render_rgb(self, vertices, faces, textures, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
+        return self._rasterize(vertices, faces, textures, (K, R, t, dist_coeffs, orig_size))["rgb"]
+
+    def render_depth(self, vertices, faces, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
+        return self._rasterize(vertices, faces, None, (K, R, t, dist_coeffs, orig_size))["depth"]
+
+    def render_silhouettes(self, vertices, faces, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
+        return self._rasterize(vertices, faces, None, (K, R, t, dist_coeffs, orig_size))["alpha"]

@@ -1,0 +1,238 @@
+"""Render fitted SMPL + object meshes over the input photo and from the side.
+
+Provides the names that `utils/render_utils.py` of a CHORE checkout exports (SMPL_OBJ_COLOR_LIST, NrWrapper, cal_norm_scale,
+get_faces_and_textures, get_kinect_K, setup_renderer, setup_side_renderer, align_to_input, load_mesh) with the same call
+signatures and results, written against this package: the renderer is chore_amd.render.Renderer (HIP rasteriser), a mesh
+is any object with `.v` (V,3) and `.f` (F,3) (`Mesh` below), PLY files are read by chore_amd.recon.assets.read_ply, and the
+resize inside `align_to_input` is ImagePrep.resize (chore_prep_resize_u8; its parity with cv2.resize is unpinned, see
+chore_amd/data/image_prep.py).  No cv2, psbody or neural_renderer import.  What these functions compute is pinned by
+tests/golden/render_host.npz, recorded from the checkout's own module.  Not provided: setup_renderer's view='top', which
+nothing in the checkout calls.
+
+`render_fit_views` is the rendering tail of the checkout's demo.py (demo.py:37-53) in one call, from decoded arrays (file
+IO stays with the caller).
+"""
+import os
+
+import numpy as np
+import torch
+
+from .. import render as nr
+
+SMPL_OBJ_COLOR_LIST = [
+    [0.65098039, 0.74117647, 0.85882353],      # body
+    [251 / 255.0, 128 / 255.0, 114 / 255.0],   # object
+]
+TEXTURE_SIZE = 4                               # texels per edge of a face's (uniform) colour cube
+# colour camera of the Kinect at its native 2048-px width
+KINECT_WIDTH = 2048
+KINECT_FOCAL = (979.784, 979.840)
+KINECT_CENTRE = (1018.952, 779.486)
+MEAN_CROP_CENTER = (1008, 995)                 # where the in-the-wild loader moves every crop centre to
+_FLIP_Y = np.array([1.0, -1.0, 1.0])           # look_at views have y up, the Kinect camera has y down
+
+
+class Mesh:
+    """vertices `.v` (V,3) float64 and faces `.f` (F,3): what this module reads of a mesh"""
+
+    def __init__(self, v=None, f=None, filename=None):
+        if filename is not None:
+            self.load_from_file(filename)
+        if v is not None:
+            self.v = np.array(v, dtype=np.float64)
+        if f is not None:
+            self.f = np.array(f)
+
+    def load_from_file(self, filename):
+        from ..recon.assets import read_ply
+        self.v, self.f = read_ply(filename)
+        return self
+
+
+def load_mesh(pcfile):
+    """the mesh of a PLY file, None when the file does not exist"""
+    return Mesh(filename=pcfile) if os.path.isfile(pcfile) else None
+
+
+def cal_norm_scale(meshes, maxd=2.0):
+    """the factor that brings the longest edge of the meshes' common bounding box to `maxd`"""
+    pts = np.concatenate([np.asarray(m.v) for m in meshes], axis=0)
+    extent = pts.max(axis=0) - pts.min(axis=0)
+    return (maxd / extent).min()
+
+
+def get_faces_and_textures(verts_list, faces_list, colors_list=SMPL_OBJ_COLOR_LIST):
+    """several meshes as one: verts_list [(B,V_i,3)], faces_list [(F_i,3) int], one colour each -> faces (1, sum B F_i, 3)
+    that index the vertices concatenated mesh after mesh, and uniform textures (1, sum B F_i, 4, 4, 4, 3)"""
+    faces_out, tex_out, first = [], [], 0
+    for verts, faces, color in zip(verts_list, faces_list, colors_list):
+        copies, per_copy = verts.shape[0], verts.shape[1]
+        starts = first + per_copy * torch.arange(copies, device=verts.device)
+        shifted = faces.unsqueeze(0) + starts.view(copies, 1, 1).to(faces.dtype)
+        faces_out.append(shifted.reshape(-1, 3))
+        first += copies * per_copy
+        cube = torch.tensor(color, dtype=torch.float32, device=verts.device).expand(TEXTURE_SIZE, TEXTURE_SIZE, TEXTURE_SIZE, 3)
+        tex_out.append(cube.unsqueeze(0).repeat(copies * faces.shape[0], 1, 1, 1, 1))
+    return torch.cat(faces_out, 0).unsqueeze(0), torch.cat(tex_out, 0).unsqueeze(0)
+
+
+def get_kinect_K(image_size=2048):
+    """(K (1,3,3), ratio): the Kinect intrinsics for a rendering `image_size` pixels wide"""
+    ratio = image_size / float(KINECT_WIDTH)
+    K = torch.eye(3, dtype=torch.float32)
+    K[0, 0], K[1, 1] = KINECT_FOCAL[0] * ratio, KINECT_FOCAL[1] * ratio
+    K[0, 2], K[1, 2] = KINECT_CENTRE[0] * ratio, KINECT_CENTRE[1] * ratio
+    return K.unsqueeze(0), ratio
+
+
+def _soft_light(renderer, ambient, direction):
+    # The checkout stores the directional intensity 0.3 under `light_intensity_direction`, a name its renderer never reads, so
+    # there the constructor's 0.5 stays in force.  Here the 0.3 is applied (and kept under the other name too): with the
+    # un-normalised direction of the front view the light factor spans 0.4 .. 0.4 + 0.3 * 1.5.
+    renderer.light_intensity_ambient = ambient
+    renderer.light_intensity_directional = renderer.light_intensity_direction = 0.3
+    renderer.light_direction = direction
+    renderer.background_color = [1, 1, 1]
+    return renderer
+
+
+def setup_renderer(view='front', rotate=False, image_size=2048):
+    """the Kinect colour camera as a square `image_size` rendering (the 2048 x 1536 frame is its upper part);
+    rotate=True turns the camera by 180 degrees about its axis"""
+    if view != 'front':
+        raise NotImplementedError("only the front view is provided, got view=%r" % (view,))
+    K, ratio = get_kinect_K(image_size)
+    turn = -1.0 if rotate else 1.0
+    R = torch.diag(torch.tensor([turn, turn, 1.0])).unsqueeze(0)
+    renderer = nr.Renderer(image_size=image_size, K=K, R=R, t=torch.zeros(1, 3), orig_size=KINECT_WIDTH * ratio)
+    return _soft_light(renderer, 0.4, [1, 0.5, 1])
+
+
+def setup_side_renderer(dist=2.0, elev=45., azim=90., image_size=640):
+    """a look_at camera on a sphere around the origin, lit from where it stands; for meshes centred at the origin"""
+    renderer = nr.Renderer(camera_mode='look_at', image_size=image_size)
+    renderer.eye = nr.get_points_from_angles(dist, elev, azim)
+    return _soft_light(renderer, 0.5, [c / 2.2 for c in renderer.eye])
+
+
+class NrWrapper:
+    """front renderer plus the tensor preparation of a list of meshes"""
+
+    def __init__(self, device='cuda:0', image_size=1024, colors=None):
+        self.device = device
+        self.colors = [list(c) for c in SMPL_OBJ_COLOR_LIST] if colors is None else colors
+        self.smpl_color, self.obj_color = SMPL_OBJ_COLOR_LIST
+        self.front_renderer = setup_renderer(image_size=image_size)
+
+    def render(self, renderer, verts, faces, texts):
+        """-> image (S,S,3) float in [0,1], mask (S,S) bool: the pixels with any covered sample"""
+        rgb, _, alpha = renderer.render(vertices=verts, faces=faces, textures=texts)
+        image = rgb[0].permute(1, 2, 0).clamp(0, 1).cpu().numpy()
+        return image, (alpha[0] != 0).cpu().numpy()
+
+    def render_meshes(self, renderer, meshes: list, colors=None):
+        """render the meshes (body, object, ...) in self.colors or `colors`"""
+        return self.render(renderer, *self.prepare_render(meshes, colors))
+
+    def prepare_render(self, meshes, colors=None):
+        """-> vertices (1, sum V, 3) float32, faces (1, sum F, 3) int32, textures (1, sum F, 4, 4, 4, 3) on self.device"""
+        palette = self.colors if colors is None else colors
+        pairs = list(zip(meshes, palette))
+        verts = [torch.as_tensor(np.asarray(m.v), dtype=torch.float32).to(self.device)[None] for m, _ in pairs]
+        faces = [torch.as_tensor(np.asarray(m.f).astype(np.int32)).to(self.device) for m, _ in pairs]
+        all_faces, textures = get_faces_and_textures(verts, faces, colors_list=[c for _, c in pairs])
+        return torch.cat(verts, dim=1), all_faces, textures
+
+    def prepare_side_rend(self, meshes, maxd=1.5, colors=None):
+        """tensors for setup_side_renderer: y flipped, scaled so that the bounding box measures `maxd`, centred at the
+        vertex mean.  The caller's meshes are not modified.  -> faces, textures, vertices"""
+        scaled = self.normalize_meshes(self.rotate_meshes(meshes), maxd=maxd)
+        verts, faces, textures = self.prepare_render(scaled, colors=colors)
+        return faces, textures, verts - verts.mean(dim=1)
+
+    @staticmethod
+    def normalize_meshes(meshes, maxd=2.0, ret_scale=False):
+        """scale the meshes IN PLACE by cal_norm_scale(meshes, maxd); returns them (and the scale on request)"""
+        scale = cal_norm_scale(meshes, maxd)
+        for mesh in meshes:
+            mesh.v = scale * np.asarray(mesh.v)
+        return (meshes, scale) if ret_scale else meshes
+
+    def rotate_meshes(self, meshes):
+        """copies of the meshes with y flipped"""
+        flipped = [self.copy_mesh(m) for m in meshes]
+        for mesh in flipped:
+            mesh.v = mesh.v * _FLIP_Y
+        return flipped
+
+    def copy_mesh(self, mesh):
+        """an independent Mesh with the vertices, faces and vertex colours (`vc`) of `mesh`, as far as it has them"""
+        twin = Mesh(v=mesh.v, f=getattr(mesh, 'f', None))
+        if hasattr(mesh, 'vc'):
+            twin.vc = np.array(mesh.vc)
+        return twin
+
+
+def _resize_u8(img, dsize, device):
+    """cv2.resize(img, dsize) for uint8 images; equal sizes are a copy (as in cv2)"""
+    if (img.shape[1], img.shape[0]) == (int(dsize[0]), int(dsize[1])):
+        return img.copy()
+    from ..data.image_prep import ImagePrep
+    return ImagePrep(device=device).resize(np.ascontiguousarray(img), dsize).cpu().numpy()
+
+
+def _window(img, lo, hi, frame, fill):
+    """the window [lo, hi) (x, y corners) of the part of `img` inside `frame` (width, height); outside is `fill`"""
+    (x0, y0), (x1, y1) = (int(c) for c in lo), (int(c) for c in hi)
+    cx0, cy0, cx1, cy1 = max(x0, 0), max(y0, 0), min(x1, frame[0]), min(y1, frame[1])
+    out = np.full((y1 - y0, x1 - x0) + img.shape[2:], fill, dtype=img.dtype)
+    if cx1 > cx0 and cy1 > cy0:
+        out[cy0 - y0:cy1 - y0, cx0 - x0:cx1 - x0] = img[cy0:cy1, cx0:cx1]
+    return out
+
+
+def align_to_input(crop_info, height, rend, train_crop_size, width, mean_cent=False, pad_value=255, device="cuda:0"):
+    """Bring a rendering of the square camera frame into the frame of the (resized) input photo.
+
+    The network saw a crop of `train_crop_size` pixels of the photo, which the loader had cut with side crop_info['crop_size']
+    around crop_info['crop_center'] and -- for in-the-wild data, mean_cent=True -- moved to MEAN_CROP_CENTER.  So the same
+    window is cut out of `rend` ((S,S) or (S,S,3) uint8, of which the `width` x `height` part counts), resized to the
+    loader's crop size and pasted at the crop centre into a canvas of crop_info['rgb_newsize'] = (w, h) filled with `pad_value`.
+    -> (h,w) or (h,w,3) uint8"""
+    w, h = (int(s) for s in crop_info['rgb_newsize'])
+    centre = np.asarray(crop_info['crop_center']).astype(int)
+    side = int(crop_info['crop_size'][0])
+    half = train_crop_size // 2
+    seen_at = np.array(MEAN_CROP_CENTER) if mean_cent else centre
+    patch = _window(rend, seen_at - half, seen_at + half, (width, height), pad_value)
+    patch = _resize_u8(patch, (side, side), device)
+    # paste the patch with its corner at centre - side // 2, clipped to the canvas
+    x0, y0 = (int(c) for c in centre - side // 2)
+    canvas = np.full((h, w) + rend.shape[2:], pad_value, dtype=np.uint8)
+    cx0, cy0, cx1, cy1 = max(x0, 0), max(y0, 0), min(x0 + side, w), min(y0 + side, h)
+    if cx1 > cx0 and cy1 > cy0:
+        canvas[cy0:cy1, cx0:cx1] = patch[cy0 - y0:cy1 - y0, cx0 - x0:cx1 - x0]
+    return canvas
+
+
+def render_fit_views(rgb_u8, crop_info, smpl_mesh, obj_mesh, load_size, nrwrapper=None, side_renderer=None, height=1536,
+                     width=2048, mean_cent=True, maxd=1.8, device="cuda:0"):
+    """the rendering half of the checkout's demo.py (:37-53) from decoded arrays.
+    rgb_u8 (oh,ow,3) uint8 RGB photo, crop_info the loader's dict, meshes with .v / .f, load_size = args.loadSize.
+    -> (overlap_u8 (oh,ow,3): the photo with the front rendering pasted where it covers, side_u8 (S,S,3): the side view
+    of `side_renderer`, 640 px by default).  `nrwrapper` / `side_renderer` can be passed to reuse them across frames."""
+    nrwrapper = NrWrapper(device=device, image_size=width) if nrwrapper is None else nrwrapper
+    side_renderer = setup_side_renderer(2.0, 0., 90.) if side_renderer is None else side_renderer
+    rgb_u8 = np.ascontiguousarray(rgb_u8)
+    oh, ow = rgb_u8.shape[:2]
+    photo = _resize_u8(rgb_u8, crop_info['rgb_newsize'], device)
+    rend, mask = nrwrapper.render_meshes(nrwrapper.front_renderer, [smpl_mesh, obj_mesh])
+    rend = (rend * 255).astype(np.uint8)
+    mask = (mask * 255).astype(np.uint8)
+    rend_in_photo = align_to_input(crop_info, height, rend, load_size, width, mean_cent, device=device)
+    covered = align_to_input(crop_info, height, mask, load_size, width, mean_cent, 0, device=device) > 127
+    photo[covered] = rend_in_photo[covered]
+    overlap = _resize_u8(photo, (ow, oh), device)
+    faces, texts, verts = nrwrapper.prepare_side_rend([smpl_mesh, obj_mesh], maxd=maxd)
+    side, _ = nrwrapper.render(side_renderer, verts, faces, texts)
+    return overlap, (side * 255).astype(np.uint8)

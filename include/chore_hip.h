@@ -312,6 +312,29 @@ int chore_sil_project_bwd(chore_handle* h, const float* verts, const float* obj_
                           const float* g_tri, float* d_obj_R, float* d_obj_t, float* d_obj_s, chore_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Colour / depth / coverage rendering of meshes, forward only  (replaces what Renderer.render gets from neural_renderer's
+ * rasterize_rgbad, external/neural_renderer/neural_renderer/rasterize.py:267-348: forward_face_index_map,
+ * forward_texture_sampling, forward_background and forward_alpha_map of cuda/rasterize_cuda_kernel.cu:24-288 at image
+ * size `size * ssaa`, the vertical flip and the 2x2 average of anti_aliasing=True).
+ * tri (B,F,3,3) projected triangles [u, v in [-1,1], depth] with both windings already in the list; textures
+ * (B,F,ts,ts,ts,3), ts >= 2; light (B,F,3) per-face factor or NULL = 1 (the reference multiplies the textures by it
+ * beforehand, lighting.py:55-56; here the blended texel is multiplied); background3: HOST, 3 floats; ssaa 1 or 2.
+ * Per sample: the hit rule of chore_silhouette_fwd at size * ssaa (the winning face is bit-identical to it: smallest
+ * depth, then smallest face index; no face is dropped; a sample is tested against exactly the triangles whose box meets
+ * its aligned 16 x 16-sample tile, as there, so zero-area triangles resolve alike too), colour = trilinear blend of the face's texture cube at
+ * clamp(w_k (ts-1) zp / z_k, 0, ts-1-tex_eps) times light, background3 where nothing was hit; depth zp or far_z; alpha 1 or 0.
+ * Outputs are resolved: row r holds sample rows of block size-1-r (the reference's flip), the mean over the ssaa x ssaa
+ * samples for rgb (B,3,size,size), depth (B,size,size) and alpha (B,size,size) alike.  sample_face_index
+ * (B,size*ssaa,size*ssaa) int32 or NULL: the winner of every sample, -1 = none, rows NOT flipped (like
+ * chore_silhouette_fwd).  size * ssaa <= 4096.  chore_render_workspace_bytes depends on the shapes only (0 = unsupported
+ * shape); nothing is allocated and no device value is read by the host, so the call can be captured into a graph.
+ * ------------------------------------------------------------------------------------------- */
+size_t chore_render_workspace_bytes(int B, int F, int size, int ssaa);
+int chore_render_fwd(chore_handle* h, const float* tri, const float* textures, const float* light, int B, int F, int ts,
+                     int size, int ssaa, float near_z, float far_z, float tex_eps, const float* background3, float* rgb,
+                     float* depth, float* alpha, int* sample_face_index, void* workspace, chore_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Evaluation metrics, fp64  (replace recon/eval/chamfer_distance.py:10-52 = sklearn kd-tree nearest neighbours, and
  * recon/eval/pose_utils.py compute_transform :145-180 / compute_similarity_transform :103-143).
  *   chore_eval_chamfer   out[0] = mean_i min_j |x_i - y_j| (direction 'x_to_y'), out[1] = the other direction
