@@ -3,6 +3,7 @@
     python -m chore_amd.dropin demo.py chore-release -s example/...          (from the root of a CHORE checkout)
     python -m chore_amd.dropin recon/recon_fit_behave.py chore-release -sn test -s <sequence>
     python -m torch.distributed.run --nproc-per-node 8 -m chore_amd.dropin train_launch.py -en chore-release
+    python -m chore_amd.dropin preprocess/preprocess_scale.py -s <sequence>
 
 `install()` registers the hot-path modules of this package under the import names the reference's scripts use
 (`from model import CHORE` /root/reference/model/__init__.py:1, `from recon.generator import Generator`,
@@ -11,11 +12,12 @@
     model, model.chore, model.camera, model.geometry
     recon, recon.generator, recon.recon_fit_base, recon.recon_fit_behave, recon.recon_fit_coco, recon.obj_pose_roi,
     recon.eval.chamfer_distance, recon.eval.pose_utils
-    lib_smpl, lib_smpl.const, lib_smpl.wrapper_pytorch, lib_smpl.smpl_generator
+    lib_smpl, lib_smpl.const, lib_smpl.wrapper_pytorch, lib_smpl.smpl_generator, lib_smpl.body_landmark
     utils, utils.render_utils, neural_renderer, neural_renderer.renderer
+    preprocess, preprocess.boundary_sampler
 
 resolve to chore_amd's classes, while every submodule this package does not replace (recon.opt_utils, recon.bbox,
-lib_smpl.body_landmark, utils.dist_utils, data.*, behave.*, config.*, trainer.*) is still found in the reference checkout:
+preprocess.preprocess_scale, utils.dist_utils, data.*, behave.*, config.*, trainer.*) is still found in the reference checkout:
 the alias packages get the checkout's directories appended to their search path.  Nothing is copied and no file of the
 reference is modified.  With `utils.render_utils` and `neural_renderer` aliased, demo.py's rendering half (the overlay and the
 side view) runs on the HIP rasteriser; its `cv2` (JPEG reading / writing, a CPU library) is the user's own.
@@ -47,6 +49,9 @@ ALIASES = {
     "utils.render_utils": "chore_amd.utils.render_utils",
     "neural_renderer": "chore_amd.render",
     "neural_renderer.renderer": "chore_amd.render.renderer",
+    "lib_smpl.body_landmark": "chore_amd.lib_smpl.body_landmark",
+    "preprocess": "chore_amd.preprocess",
+    "preprocess.boundary_sampler": "chore_amd.preprocess.boundary_sampler",
 }
 
 

@@ -645,6 +645,23 @@ int chore_fit_obj_terms_bwd(chore_handle* h, const float* diff, const float* obj
 int chore_fit_rot_noise(chore_handle* h, const float* rot, const float* noise, int64_t* k, float scale, int B, int64_t steps,
                         float* out, chore_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Exact unsigned distance from points to a triangle mesh, forward only  (what the training-data sampler takes from
+ * np.abs(igl.signed_distance(P, V, F)[0]), its I and C, and from trimesh.proximity.ProximityQuery(mesh).vertex(P)[1]:
+ * preprocess/boundary_sampler.py:45-64).  points (B,N,3), verts (B,V,3) fp32, faces (F,3) int32 shared by the batch.
+ *   dist (B,N)        Euclidean distance to the triangle SURFACE of mesh b: the minimum over all F triangles (interior, edge
+ *                     and vertex regions), brute force, no approximation
+ *   face_idx (B,N)    a triangle that attains it: smallest fp32 squared distance, then smallest face index; NULL = not wanted
+ *   closest (B,N,3)   the closest point on that triangle; NULL = not wanted
+ *   vert_idx (B,N)    the nearest mesh VERTEX: smallest fp32 squared distance, then smallest index; NULL = not wanted
+ * A zero-area triangle counts as the segment or point it degenerates to; finite inputs give finite outputs.  The optional
+ * outputs do not change the bits of the others.  chore_mesh_dist_workspace_bytes depends on the shapes only (0 = unsupported
+ * shape); nothing is allocated and no device value is read by the host, so the call can be captured into a graph.
+ * ------------------------------------------------------------------------------------------- */
+size_t chore_mesh_dist_workspace_bytes(int B, int N, int V, int F);
+int chore_mesh_dist_fwd(chore_handle* h, const float* points, const float* verts, const int* faces, int B, int N, int V, int F,
+                        float* dist, int* face_idx, float* closest, int* vert_idx, void* workspace, chore_stream_t stream);
+
 /* debug aid: with CHORE_NAN_CHECK=1 in the environment chore_query_fwd / chore_query_bwd_points scan their inputs and
  * outputs for non-finite values (extra launches on the caller's stream); out32[0..15] = counts per site (0 points, 1-4 the
  * forward's df / pca / parts / centers, 5 / 6 the maps, 8 points, 9-12 the upstream gradients, 13 dpoints), out32[16..31] =
