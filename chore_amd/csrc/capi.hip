@@ -160,6 +160,14 @@ extern "C" int chore_debug_nan_counts(unsigned* out32) {
     return hipMemcpyFromSymbol(out32, HIP_SYMBOL(g_nan_counts), sizeof(unsigned) * 32) == hipSuccess ? 0 : -2;
 }
 
+// what the last convolution launch on the handle chose (chore_handle::last_conv): up to 8 ints, returns how many were written
+extern "C" int chore_debug_last_conv(chore_handle* h, int* out, int n) {
+    if (!h || !out || n <= 0) return CHORE_EINVAL;
+    const int k = n < 8 ? n : 8;
+    for (int i = 0; i < k; ++i) out[i] = h->last_conv[i];
+    return k;
+}
+
 // split a query dtype into the map type and the heads mode (include/chore_hip.h: CHORE_HEADS_X3)
 static inline bool query_x3(int& dtype) {
     const bool x3 = dtype == CHORE_F16X3 || dtype == CHORE_F16 || (dtype & CHORE_HEADS_X3);      // fp16 maps: always with these heads

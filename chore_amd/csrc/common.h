@@ -24,7 +24,17 @@ struct chore_handle {
     hipEvent_t side_ev[8] = {};
     int cu_count = 0;          // hipDeviceAttributeMultiprocessorCount of `device`, read on first use (chore_cu_count_cached)
     int lds_per_cu = 0;        // hipDeviceAttributeMaxSharedMemoryPerMultiprocessor of `device`, read on first use (chore_lds_per_cu)
+    // what the last convolution launch on this handle chose (chore_debug_last_conv): family, rows, nt, tps, nslot, flags, Cin,
+    // and the number of convolution launches so far.  Host stores only; tests assert from it which kernel a shape reaches
+    int last_conv[8] = {};
 };
+// kernel families and flag bits of chore_handle::last_conv (include/chore_hip.h, chore_debug_last_conv)
+enum { CONV_FAM_LDS = 1, CONV_FAM_SMALL = 2, CONV_FAM_PC = 3, CONV_FAM_MW = 4, CONV_FAM_RW = 5 };
+enum { CONV_FLAG_SCALED = 1, CONV_FLAG_GN = 2, CONV_FLAG_SMALL_GRID = 4, CONV_FLAG_RES = 8 };
+inline void chore_note_conv(chore_handle* h, int family, int rows, int nt, int tps, int nslot, int flags, int cin) {
+    int* r = h->last_conv;
+    r[0] = family; r[1] = rows; r[2] = nt; r[3] = tps; r[4] = nslot; r[5] = flags; r[6] = cin; ++r[7];
+}
 
 // every entry point runs with the handle's device current (a caller whose current device is another GPU -- e.g. the
 // reference's model.to(torch.device(opt.gpu_id)) without torch.cuda.set_device -- would otherwise create the encoder's

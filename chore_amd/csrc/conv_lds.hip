@@ -596,6 +596,8 @@ int launch_conv(chore_handle* h, int dtype, int taps, const ConvArgs& a_in, hipS
 #endif
     const int nt = choose_nt(dtype, a.B, a.H, a.W, a.Cout);
     const bool small_grid = is_small_grid(dtype, a.B, a.H, a.W, a.in.C, a.Cout, nt);
+    // (taps per K-step as conv_plan derives them and as launch_nt instantiates them below: 9 for the small grid, else 3; keep the three alike)
+    chore_note_conv(h, CONV_FAM_LDS, TH, nt, taps == 1 ? 1 : (small_grid ? 9 : 3), 2, conv_note_flags(a, small_grid), a.in.C);
     if (dtype == CHORE_F32)
         return taps == 9 ? launch_nt<float, 9>(h, nt, small_grid, a, s) : launch_nt<float, 1>(h, nt, small_grid, a, s);
     if (dtype == CHORE_F16X3)

@@ -730,6 +730,7 @@ bool conv_mw_covers(int dtype, int taps, const PcPlan& p, const ConvArgs& a) {
 }
 
 int launch_conv_mw(chore_handle* h, int dtype, int taps, const PcPlan& p, const ConvArgs& a, hipStream_t s) {
+    chore_note_conv(h, CONV_FAM_MW, p.th, p.nt, p.tps, p.nslot, conv_note_flags(a), a.in.C);
     const int key = (p.th * 1000 + p.nt) * 100 + p.tps * 10 + p.nslot;
 #define MW_CASE(TH, NT, TPS, NSLOT) \
     case (TH * 1000 + NT) * 100 + TPS * 10 + NSLOT:                                              \

@@ -419,6 +419,7 @@ static int launch_conv_rw_t(chore_handle* h, const ConvArgs& a, hipStream_t s) {
 }
 
 int launch_conv_rw(chore_handle* h, int dtype, const ConvArgs& a, hipStream_t s) {
+    chore_note_conv(h, CONV_FAM_RW, 0, a.Cout, 1, 0, conv_note_flags(a), a.in.C);
     if (dtype == CHORE_F16) return launch_conv_rw_t<h16_t>(h, a, s);
     if (dtype == CHORE_BF16) return launch_conv_rw_t<bf16_t>(h, a, s);
     if (dtype == CHORE_F16X3) return launch_conv_rw_t<x3_t>(h, a, s);

@@ -419,6 +419,7 @@ bool conv_small_eligible(int dtype, int taps, int H, int W, int Cin, int Cout) {
 int launch_conv_small(chore_handle* h, int dtype, const ConvArgs& a, hipStream_t s) {
     if ((size_t)a.B * a.H * (a.W / 32) * (a.Cout / 32) > 0x7fffffffull) CHORE_FAIL(h, CHORE_EINVAL, "conv_small: grid too large");
     const int rows = small_rows(dtype, a.H, a.W, a.in.C);
+    chore_note_conv(h, CONV_FAM_SMALL, rows, 32, 9, 0, conv_note_flags(a), a.in.C);
     if (dtype == CHORE_F16) return launch_small_c<h16_t>(h, rows, a, s);
     if (dtype == CHORE_F16X3 && a.in_amax) return launch_small_c<x3s_t>(h, rows, a, s);
     return dtype == CHORE_F16X3 ? launch_small_c<x3_t>(h, rows, a, s) : launch_small_c<bf16_t>(h, rows, a, s);

@@ -246,6 +246,12 @@ template <> struct Vec4<h16_t> {
 };
 #endif
 
+// the flag word of chore_handle::last_conv for a launch with these arguments
+inline int conv_note_flags(const ConvArgs& a, bool small_grid = false) {
+    return (a.in_amax ? CONV_FLAG_SCALED : 0) | (a.in_st ? CONV_FLAG_GN : 0) | (small_grid ? CONV_FLAG_SMALL_GRID : 0) |
+           (a.res.p ? CONV_FLAG_RES : 0);
+}
+
 struct ConvPlan { int nt, th, ntiles, tps, small_cin; };   // N tile, tile height, tiles per image, taps per K-step (tps 0: conv_small_kernel)
 // small maps (conv_small.hip): one workgroup = 32 pixels of a row x 32 output channels, K split over its four waves
 bool conv_small_eligible(int dtype, int taps, int H, int W, int Cin, int Cout);

@@ -11,7 +11,8 @@
 extern "C" {
 
 size_t chore_conv2d_workspace_bytes(int dtype, int taps, int Cin, int Cout) {
-    if ((dtype != CHORE_F32 && dtype != CHORE_BF16 && dtype != CHORE_F16X3) || (taps != 1 && taps != 9)) return 0;
+    // CHORE_F16 (half tensors) reads its weights in the fp16 x 3 layout: hi plane + lo plane (launch_pack_conv)
+    if ((dtype != CHORE_F32 && dtype != CHORE_BF16 && dtype != CHORE_F16X3 && dtype != CHORE_F16) || (taps != 1 && taps != 9)) return 0;
     return packed_conv_bytes(dtype, taps, Cin, Cout);
 }
 

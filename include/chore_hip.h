@@ -667,6 +667,16 @@ int chore_mesh_dist_fwd(chore_handle* h, const float* points, const float* verts
  * forward's df / pca / parts / centers, 5 / 6 the maps, 8 points, 9-12 the upstream gradients, 13 dpoints), out32[16..31] =
  * sequence number of the first scan of that site that saw one */
 int chore_debug_nan_counts(unsigned* out32);
+/* debug aid: what the last convolution launch on the handle (chore_conv2d_fwd, chore_conv2d_bwd_data, every layer of the encoder
+ * and of the training operators) chose.  Writes min(n, 8) ints and returns that count (negative: bad argument):
+ *   out[0] kernel family: 1 conv_lds_kernel, 2 conv_small_kernel, 3 conv_pc_kernel, 4 conv_mw_kernel, 5 conv_rw_kernel (0: none yet)
+ *   out[1] rows of a tile (conv_small_kernel: rows per workgroup; conv_rw_kernel: 0)   out[2] output channels per workgroup
+ *   out[3] taps per K-step   out[4] K-steps of weights resident in LDS (0 where the kernel has no such ring)
+ *   out[5] flags: 1 scaled-input variant (data gradient of CHORE_F16X3), 2 GroupNorm fused into the input, 4 small-grid variant
+ *          of conv_lds_kernel, 8 residual added in the epilogue
+ *   out[6] input channels   out[7] convolution launches on the handle so far
+ * Host stores only: no kernel and no result changes. */
+int chore_debug_last_conv(chore_handle* h, int* out, int n);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,8 @@ import sys
 import numpy as np
 import pytest
 
+from conv_ref import stat_values      # the decoder of the statistics cells, shared with test_gpu_conv_kernels.py
+
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -72,14 +74,6 @@ def run(tmp_path, script, tag, env, **kw):
     r = subprocess.run([sys.executable, "-c", script.format(repo=REPO, path=path, **kw)], env=e, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     return dict(np.load(path))
-
-
-def stat_values(cells):
-    """[2 tables][B][32] GroupStat (sum, sq) x (lo, hi) limbs -> the totals as float64 (enc_common.h stat_read)"""
-    c = cells.reshape(2, -1, 2, 2)               # table, (image, group), sum / sq, limb
-    lo = c[0, :, :, 0].astype(np.uint64)
-    top = c[1, :, :, 1].astype(np.float64) + (lo >> np.uint64(32)).astype(np.float64)
-    return (top * 2.0 ** 32 + (lo & np.uint64(0xffffffff)).astype(np.float64)) * 2.0 ** -40
 
 
 def test_layers_equal_conv_pc_bit_for_bit(tmp_path):

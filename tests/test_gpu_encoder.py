@@ -104,16 +104,25 @@ def test_encoder_fp16_modes_on_a_ragged_shape(opt, net32):
             assert rel_l2(a, b) < tol_l2, (mode, name, rel_l2(a, b))
 
 
-@pytest.mark.parametrize("mode", ["fp32", "bf16"])
-def test_encoder_512_checksums(net32, net16, mode):
-    """BASELINE size (512x512) against per-channel statistics and crops of the reference output"""
+@pytest.mark.parametrize("mode,B", [pytest.param(m, b, id=m if b == 1 else "%s-b%d" % (m, b))
+                                    for b in (1, 4) for m in ("fp32", "bf16", "fp16x3", "fp16")])
+def test_encoder_512_checksums(request, opt, mode, B):
+    """BASELINE size (512x512) against per-channel statistics and crops of the reference output, in every compute mode; B = 4 (the
+    benchmark's batch: other tilings, residual epilogues, strided slice outputs and raw copies at production size) stacks the
+    golden's image first with three others and compares image 0.  fp16x3 is held to the fp32 bounds, as everywhere in the project;
+    fp16 (half maps, three more mantissa bits than bf16) to the bf16 bounds."""
+    import copy
     from chore_amd.utils import synth
-    net = net32 if mode == "fp32" else net16
+    net = (request.getfixturevalue("net32") if mode == "fp32" else request.getfixturevalue("net16") if mode == "bf16"
+           else make_net(copy.copy(opt), mode))
     g = golden("encoder_512_checksum.npz")
-    outs, tmpx, _ = encode(net, synth.synth_images(1, 512, 512, seed=0), train=False)
-    out = outs[0]
-    assert out.shape == (1, 256, 128, 128)
-    tol_max, tol_mean = (3e-4, 2e-4) if mode == "fp32" else (1e-1, 1e-2)
+    images = synth.synth_images(1, 512, 512, seed=0)
+    if B > 1:
+        images = np.concatenate([images, synth.synth_images(B - 1, 512, 512, seed=1)])
+    outs, tmpx, _ = encode(net, images, train=False)
+    assert outs[0].shape == (B, 256, 128, 128)
+    out, tmpx = outs[0][:1], tmpx[:1]
+    tol_max, tol_mean = (3e-4, 2e-4) if mode in ("fp32", "fp16x3") else (1e-1, 1e-2)
     assert rel_max(out[:, :, 60:68, 100:108], g["out_crop"]) < tol_max
     assert rel_max(tmpx[:, :, 128:132, 200:204], g["tmpx_crop"]) < tol_max
     s = np.abs(g["out_absmean"]).max()
