@@ -177,6 +177,11 @@ SIGNATURES = {
                                         c_int, c_void_p, c_void_p]),
     "chore_prep_crop_compose_mean": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_double, ctypes.c_double,
                                              ctypes.c_double, ctypes.c_double, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "chore_prep_blur_max_radius": (c_int, []),
+    "chore_prep_blur_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "chore_prep_blur_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "chore_prep_train_compose": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                         c_void_p, c_void_p]),
     "chore_collision_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "chore_collision_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p]),

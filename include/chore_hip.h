@@ -417,6 +417,33 @@ int chore_prep_crop_compose_mean(chore_handle* h, const unsigned char* rgb, cons
                                  const unsigned char* obj_mask, int H, int W, double cc_x, double cc_y, double mean_x, double mean_y,
                                  int tl_x, int tl_y, int br_x, int br_y, int S, float* images, chore_stream_t stream);
 
+/* Image preparation of the TRAINING loader (BehaveDataset.prepare_image_crop data/train_data.py:134-149 on BaseDataset
+ * data/base_data.py:71-192, from the decoded uint8 images on): the augmentations and the batched crop / compose.
+ *   chore_prep_blur_u8       PIL.ImageFilter.GaussianBlur on src (B, H, W, C) uint8, C <= 4, -> dst (same shape; may be
+ *                            src), bit for bit: three box-blur passes along the rows, then three along the columns, in
+ *                            PIL's 24-bit fixed point, every pass rounded to uint8.  params (B, 3) int32 ON THE DEVICE holds
+ *                            per image {R, ww, fw}: the integer part of the effective box radius, the weight of a whole
+ *                            pixel and of the two fractional end pixels (TrainImagePrep.box_params computes them from the
+ *                            PIL radius with PIL's float32 expressions); {0, 0, 0} copies the image.  max_r is the
+ *                            largest R in params, declared by the caller, who filled them: above
+ *                            chore_prep_blur_max_radius() (64, i.e. PIL radii up to about 64) the call is refused with
+ *                            CHORE_EINVAL.  Whole lines are staged through LDS, so an R beyond the image's side is
+ *                            covered; a line that does not fit the LDS (W * C above about 80 KB, H above about 20 000)
+ *                            is refused.  workspace: chore_prep_blur_workspace_bytes(B, H, W, C) bytes, the one
+ *                            intermediate image.  Two launches, no host read, no atomics, no allocation: records into a
+ *                            hipGraph.
+ *   chore_prep_train_compose chore_prep_crop_compose on a batch: rgb (B, H, W, 3), masks (B, H, W), HOST arrays
+ *                            tlbr_host (B, 4) = {tl_x, tl_y, br_x, br_y} and flip_host (B), images (B, 5, S, S) fp32.
+ *                            flip_host[b] != 0 takes the crop from the horizontal mirror of image b (column W - 1 - x of
+ *                            all three sources); without it image b's result is chore_prep_crop_compose's bit for bit. */
+int chore_prep_blur_max_radius(void);
+size_t chore_prep_blur_workspace_bytes(int B, int H, int W, int C);
+int chore_prep_blur_u8(chore_handle* h, const unsigned char* src, int B, int H, int W, int C, const int* params, int max_r,
+                       unsigned char* dst, void* workspace, chore_stream_t stream);
+int chore_prep_train_compose(chore_handle* h, const unsigned char* rgb, const unsigned char* person_mask,
+                             const unsigned char* obj_mask, int B, int H, int W, const int* tlbr_host, const int* flip_host,
+                             int S, float* images, chore_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Interpenetration term of the joint fit  (replaces ReconFitterBase.smpl_obj_collision recon/recon_fit_base.py:610-624 =
  * mesh_intersection.BVH(max_collisions=8) + DistanceFieldPenetrationLoss(sigma=0.5, point2plane=False), constructed at
