@@ -168,6 +168,14 @@ extern "C" int chore_debug_last_conv(chore_handle* h, int* out, int n) {
     return k;
 }
 
+// the same for the last weight-gradient launch (chore_handle::last_wgrad)
+extern "C" int chore_debug_last_wgrad(chore_handle* h, int* out, int n) {
+    if (!h || !out || n <= 0) return CHORE_EINVAL;
+    const int k = n < 8 ? n : 8;
+    for (int i = 0; i < k; ++i) out[i] = h->last_wgrad[i];
+    return k;
+}
+
 // split a query dtype into the map type and the heads mode (include/chore_hip.h: CHORE_HEADS_X3)
 static inline bool query_x3(int& dtype) {
     const bool x3 = dtype == CHORE_F16X3 || dtype == CHORE_F16 || (dtype & CHORE_HEADS_X3);      // fp16 maps: always with these heads

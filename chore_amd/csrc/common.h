@@ -27,6 +27,9 @@ struct chore_handle {
     // what the last convolution launch on this handle chose (chore_debug_last_conv): family, rows, nt, tps, nslot, flags, Cin,
     // and the number of convolution launches so far.  Host stores only; tests assert from it which kernel a shape reaches
     int last_conv[8] = {};
+    // the same for the last weight-gradient launch (chore_debug_last_wgrad): kernel, element type, taps, channel tile, shares,
+    // pixel tiles, flags, and the number of weight-gradient launches so far
+    int last_wgrad[8] = {};
 };
 // kernel families and flag bits of chore_handle::last_conv (include/chore_hip.h, chore_debug_last_conv)
 enum { CONV_FAM_LDS = 1, CONV_FAM_SMALL = 2, CONV_FAM_PC = 3, CONV_FAM_MW = 4, CONV_FAM_RW = 5 };
@@ -34,6 +37,13 @@ enum { CONV_FLAG_SCALED = 1, CONV_FLAG_GN = 2, CONV_FLAG_SMALL_GRID = 4, CONV_FL
 inline void chore_note_conv(chore_handle* h, int family, int rows, int nt, int tps, int nslot, int flags, int cin) {
     int* r = h->last_conv;
     r[0] = family; r[1] = rows; r[2] = nt; r[3] = tps; r[4] = nslot; r[5] = flags; r[6] = cin; ++r[7];
+}
+// kernels and flag bits of chore_handle::last_wgrad (include/chore_hip.h, chore_debug_last_wgrad)
+enum { WGRAD_K_W32 = 1, WGRAD_K_W64 = 2, WGRAD_K_W64X3 = 3, WGRAD_K_W64X3PC = 4, WGRAD_K_W128X3PC = 5 };
+enum { WGRAD_FLAG_GN = 1, WGRAD_FLAG_DBIAS = 2, WGRAD_FLAG_XCD = 4 };
+inline void chore_note_wgrad(chore_handle* h, int kernel, int elem, int taps, int ct, int S, int tiles, int flags) {
+    int* r = h->last_wgrad;
+    r[0] = kernel; r[1] = elem; r[2] = taps; r[3] = ct; r[4] = S; r[5] = tiles; r[6] = flags; ++r[7];
 }
 
 // every entry point runs with the handle's device current (a caller whose current device is another GPU -- e.g. the

@@ -1351,6 +1351,12 @@ int conv2d_bwd_weight_impl(chore_handle* h, int dtype, int taps, const void* x, 
     a.xs = Cin; a.ys = dy_stride; a.npix = (long long)B * H * W;
     a.part = (float*)workspace;
     int ct = 32;
+    // the witness of this launch (chore_debug_last_wgrad; host stores only): th = rows of the kernel's pixel tile
+    const int wflags = (stats ? WGRAD_FLAG_GN : 0) | (dbias ? WGRAD_FLAG_DBIAS : 0);
+    auto note = [&](int kernel, int elem, int th) {
+        const int tiles = kernel == WGRAD_K_W128X3PC ? (int)((long)B * H * W / W128_PX) : B * ((W + TW - 1) / TW) * ((H + th - 1) / th);
+        chore_note_wgrad(h, kernel, elem, taps, ct, a.S, tiles, wflags | (ct >= 64 && a.S % 8 == 0 ? WGRAD_FLAG_XCD : 0));
+    };
     // after a layer's partial sums are launched (rc: that launch's result): the sum over the shares now, or, with `defer`, a
     // record of it for launch_wgrad_finish_multi
     auto finish = [&](int rc) -> int {
@@ -1379,6 +1385,7 @@ int conv2d_bwd_weight_impl(chore_handle* h, int dtype, int taps, const void* x, 
             const int np128 = (Cout / 128) * (Cin / 128);
             a.part_bias = dbias ? a.part + (size_t)a.S * np128 * 16384 : nullptr;
             const size_t sm128 = (size_t)2 * 4 * W128_PX * W128_PITCH;
+            note(WGRAD_K_W128X3PC, CHORE_F16X3, 1);
             return finish(CHORE_LAUNCH(h, s, wgrad128_x3_pc_kernel, dim3(a.S * np128), dim3(512), sm128, a));
         }
         if (x3 && use_pc) {
@@ -1386,15 +1393,18 @@ int conv2d_bwd_weight_impl(chore_handle* h, int dtype, int taps, const void* x, 
             a.part_bias = dbias ? a.part + (size_t)a.S * npairs * taps * 4096 : nullptr;
             const size_t arows = taps == 9 ? (size_t)(WP_TH + 2) * PW : (size_t)WP_TH * TW;
             const size_t smp = (size_t)2 * 2 * (arows + WP_TH * TW) * W64_PITCH;
+            note(WGRAD_K_W64X3PC, CHORE_F16X3, WP_TH);
             return finish(taps == 9 ? CHORE_LAUNCH(h, s, wgrad64_x3_pc_kernel<9>, dim3(a.S * npairs), dim3(512), smp, a)
                                     : CHORE_LAUNCH(h, s, wgrad64_x3_pc_kernel<1>, dim3(a.S * npairs), dim3(512), smp, a));
         }
         if (x3) {
             const size_t smx = (size_t)2 * ((taps == 9 ? (WX_TH + 2) * PW : WX_TH * TW) + WX_TH * TW) * W64_PITCH + 64 * 2 * sizeof(float);
+            note(WGRAD_K_W64X3, CHORE_F16X3, WX_TH);
             return finish(taps == 9 ? CHORE_LAUNCH(h, s, wgrad64_x3_kernel<9>, dim3(a.S * npairs), dim3(256), smx, a)
                                     : CHORE_LAUNCH(h, s, wgrad64_x3_kernel<1>, dim3(a.S * npairs), dim3(256), smx, a));
         }
         const size_t smem64 = (size_t)((taps == 9 ? PH * PW : TH * TW) + TH * TW) * W64_PITCH + 64 * 2 * sizeof(float);
+        note(WGRAD_K_W64, CHORE_BF16, TH);
         return finish(taps == 9 ? CHORE_LAUNCH(h, s, wgrad64_kernel<9>, dim3(a.S * npairs), dim3(256), smem64, a)
                                 : CHORE_LAUNCH(h, s, wgrad64_kernel<1>, dim3(a.S * npairs), dim3(256), smem64, a));
     }
@@ -1406,6 +1416,7 @@ int conv2d_bwd_weight_impl(chore_handle* h, int dtype, int taps, const void* x, 
     size_t smem = (size_t)(arows + TH * TW) * CT32 * es + 256;
     if (smem < 4 * 1024 * sizeof(float)) smem = 4 * 1024 * sizeof(float);
     dim3 grid(Cout / 32, Cin / 32, a.S);
+    note(WGRAD_K_W32, dtype, TH);
     if (dtype == CHORE_F32)
         return finish(taps == 9 ? CHORE_LAUNCH(h, s, (wgrad_kernel<float, 9>), grid, dim3(256), smem, a)
                                 : CHORE_LAUNCH(h, s, (wgrad_kernel<float, 1>), grid, dim3(256), smem, a));
@@ -1462,6 +1473,7 @@ int chore_gemm_tn_f32(chore_handle* h, const float* A, int lda, const float* B, 
     a.part = (float*)workspace;
     a.part_bias = nullptr;
     const size_t smem = (size_t)(2 * TH * TW) * CT32 * 4 + 256;
+    chore_note_wgrad(h, WGRAD_K_W32, CHORE_F32, 1, 32, a.S, (a.H + TH - 1) / TH, 0);
     if (int rc = CHORE_LAUNCH(h, s, (wgrad_kernel<float, 1>), dim3(M / 32, N / 32, a.S), dim3(256), smem, a)) return rc;
     const size_t n = (size_t)M * N;
     hipLaunchKernelGGL(wgrad_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.part, nullptr, a.S, M, N, 1, C,

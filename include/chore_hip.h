@@ -704,6 +704,18 @@ int chore_debug_nan_counts(unsigned* out32);
  *   out[6] input channels   out[7] convolution launches on the handle so far
  * Host stores only: no kernel and no result changes. */
 int chore_debug_last_conv(chore_handle* h, int* out, int n);
+/* debug aid: what the last weight-gradient launch on the handle (chore_conv2d_bwd_weight, chore_gemm_tn_f32, every layer of
+ * chore_convblock_bwd) chose.  Writes min(n, 8) ints and returns that count (negative: bad argument):
+ *   out[0] kernel: 1 wgrad_kernel (32-channel tiles), 2 wgrad64_kernel, 3 wgrad64_x3_kernel, 4 wgrad64_x3_pc_kernel,
+ *          5 wgrad128_x3_pc_kernel (0: none yet)
+ *   out[1] element type of the arithmetic: CHORE_F32, CHORE_BF16 or CHORE_F16X3 (a CHORE_F16X3 layer below 64 channels reports
+ *          CHORE_F32: it runs the fp32 kernel)
+ *   out[2] taps   out[3] channels per tile side   out[4] shares S of the pixel tiles   out[5] pixel tiles
+ *   out[6] flags: 1 GroupNorm + ReLU recomputed on the input, 2 dbias requested, 4 the XCD-interleaved workgroup -> (share,
+ *          channel pair) mapping (S % 8 == 0 in the 64- and 128-channel kernels) instead of the linear one
+ *   out[7] weight-gradient launches on the handle so far
+ * Host stores only: no kernel and no result changes. */
+int chore_debug_last_wgrad(chore_handle* h, int* out, int n);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,9 @@
-"""The float64 reference of one encoder convolution layer, plain torch on the CPU (tests/test_gpu_conv_kernels.py).
+"""The float64 reference of one encoder convolution layer, plain torch on the CPU (tests/test_gpu_conv_kernels.py,
+tests/test_gpu_wgrad_kernels.py).
 
-  forward        y = conv2d(a, w, zero padding) + bias,  a = relu(group_norm(x, 32, gamma, beta, eps=1e-5)) when GroupNorm is fused
-  data gradient  dx = conv_transpose2d(dy, w)   (= the convolution of dy with the transposed, spatially flipped weights)
+  forward          y = conv2d(a, w, zero padding) + bias,  a = relu(group_norm(x, 32, gamma, beta, eps=1e-5)) when GroupNorm is fused
+  data gradient    dx = conv_transpose2d(dy, w)   (= the convolution of dy with the transposed, spatially flipped weights)
+  weight gradient  dW, dbias of that forward for an upstream gradient dy, by autograd
 
 Tensors are NHWC numpy arrays (what the kernels read), weights in the reference layout (O, C, kh, kw).  Everything is computed
 in float64 from the bits the device is handed: a 16-bit mode's reference sees the input rounded to the storage type first
@@ -49,6 +51,16 @@ def data_gradient(dy_stored, w):
     w = torch.from_numpy(w).double()
     dx = F.conv_transpose2d(_nchw64(dy_stored), w, padding=w.shape[-1] // 2)
     return dx.permute(0, 2, 3, 1).contiguous().numpy()
+
+
+def weight_gradient(x_stored, dy_stored, k, gamma=None, beta=None):
+    """x (B, H, W, Cin), dy (B, H, W, Cout) of the storage type -> dW (Cout, Cin, k, k), dbias (Cout), float64 numpy: autograd of
+    conv2d(a, w) + bias, a = relu(group_norm(x)) with gamma / beta, else x"""
+    a = normalised(x_stored, gamma, beta) if gamma is not None else _nchw64(x_stored)
+    w = torch.zeros(dy_stored.shape[-1], a.shape[1], k, k, dtype=torch.float64, requires_grad=True)     # (dW does not depend on w)
+    b = torch.zeros(dy_stored.shape[-1], dtype=torch.float64, requires_grad=True)
+    F.conv2d(a, w, b, padding=k // 2).backward(_nchw64(dy_stored))
+    return w.grad.numpy(), b.grad.numpy()
 
 
 def storage_model(x_stored, w, bias, gamma, beta, mode):
