@@ -1,7 +1,8 @@
 """Fitting maths of CHORE on the GPU: SO(3) projection, object transform, loss terms.
 
 Counterpart of /root/reference/recon/recon_fit_base.py (ReconFitterBase) for the methods that sit on the
-optimisation hot path; file I/O, mesh viewers and dataset glue of that class are out of scope.
+optimisation hot path; file I/O and dataset glue of that class are out of scope; its mesh viewer (-d) is
+replaced by headless point-cloud views (visualize_*, at the end of the class).
 Method names, signatures and loss-dict keys are the reference's, so recon_fit_behave-style drivers read
 the same.  Heavy steps run in libchore_hip.so: the field queries (chore_query_fwd/bwd_points), SMPL-H LBS
 (chore_smpl_lbs_*) and the SO(3) projection (chore_so3_project_*); the remaining terms are a few
@@ -540,3 +541,186 @@ class ReconFitterBase:
         with torch.no_grad():
             v = smpl()[0]
             return v[:, :, 1].max(1)[0] - v[:, :, 1].min(1)[0]
+
+    # ---- looking at a fit (recon_fit_base.py:442-511, 704-718, 749-845) ---------------------------------
+    # The reference opens a psbody MeshViewer and cv2 windows at every step; everything it shows is a point cloud.  Here the
+    # same clouds are drawn headless by the point rasteriser (chore_splat_fwd through utils/render_utils.render_cloud_views)
+    # and RETURNED as uint8 images of frame `_view_index` (0, like the reference's idx) of the batch.  Drawing draws no
+    # random numbers and leaves the network's query state as it found it.
+    VIEW_GREEN, VIEW_RED, VIEW_YELLOW, VIEW_BLUE = (0., 1., 0.), (1., 0., 0.), (1., 1., 0.), (0., 0., 1.)
+    VIEW_CYAN, VIEW_MAGENTA = (0., 1., 1.), (1., 0., 1.)
+    VIEW_VERT_R, VIEW_POINT_R = 0.005, 0.008      # world radii of SMPL vertices and of generated points, metres
+    _view_index = 0
+    debug_dest = None                             # (save_name, test_id) of the debug files; fit_recon sets it from its args
+
+    def _cloud_views(self, data_dict, smpl, clouds, colors, radii):
+        from ..utils.render_utils import CLOUD_VIEW_SIZE, render_cloud_views
+        idx = self._view_index
+        crop_center = data_dict["query_dict"]["crop_center"]
+        with torch.no_grad():
+            J, _, _ = smpl.get_landmarks()
+            pxy = self.project_points(J, crop_center)[idx, :, :2] * (CLOUD_VIEW_SIZE / float(self.net_in_size))
+        markers = [(pxy, self.VIEW_YELLOW, 3.0)]              # projected body-25 joints
+        if "body_kpts" in data_dict:                          # detected keypoints
+            markers.append((data_dict["body_kpts"][idx][:, :2] * (CLOUD_VIEW_SIZE / float(self.net_in_size)), self.VIEW_RED, 2.0))
+        return render_cloud_views(data_dict["images"][idx], crop_center[idx], clouds, colors, radii, markers, camera=self.camera)
+
+    def _human_clouds(self, data_dict, smpl_verts):
+        idx = self._view_index
+        parts = data_dict["part_colors"][idx] if "part_colors" in data_dict else \
+            self.get_parts_colors(data_dict["human_parts"])[idx]
+        return ([smpl_verts[idx].detach(), data_dict["human_init"][idx].detach()], [self.VIEW_GREEN, np.asarray(parts)],
+                [self.VIEW_VERT_R, self.VIEW_POINT_R])
+
+    def visualize_smpl_fit(self, data_dict, smpl, smpl_verts):
+        """[:749-796] SMPL vertices (green), the generator's human points (part colours), contact vertices (blue, from
+        `contact_mask`), the predicted SMPL centre as a 5 cm marker, the keypoints -> (512, 1152, 3) uint8"""
+        idx = self._view_index
+        clouds, colors, radii = self._human_clouds(data_dict, smpl_verts)
+        if "contact_mask" in data_dict and bool(data_dict["contact_mask"][idx].any()):
+            # first in the list: a contact vertex coincides with its SMPL vertex, and equal depths go to the smaller index
+            clouds.insert(0, smpl_verts[idx, data_dict["contact_mask"][idx]].detach())
+            colors.insert(0, self.VIEW_BLUE)
+            radii.insert(0, self.VIEW_VERT_R)
+        if "smpl_center_pred" in data_dict:
+            clouds.append(data_dict["smpl_center_pred"][idx].detach().reshape(1, 3))
+            colors.append(self.VIEW_YELLOW)
+            radii.append(0.05)
+        return self._cloud_views(data_dict, smpl, clouds, colors, radii)
+
+    def visualize_fitting(self, data_dict, object, smpl, smpl_verts):
+        """[:442-511] object points (red), their initial placement (yellow), SMPL vertices (green), the generator's human
+        points (part colours), contact vertices and points (blue, from `contact_mask_h` / `contact_mask_o`), the centres
+        `obj_center_pred` (cyan), `smpl_center_pred` (yellow) and `smpl_center_act` (magenta) as 6 cm markers, the
+        keypoints -> (512, 1152, 3) uint8"""
+        idx = self._view_index
+        clouds, colors, radii = [], [], []
+        for key, src in (("contact_mask_h", smpl_verts), ("contact_mask_o", object)):
+            if key in data_dict and bool(data_dict[key][idx].any()):
+                clouds.append(src[idx, data_dict[key][idx]].detach())
+                colors.append(self.VIEW_BLUE)
+                radii.append(self.VIEW_POINT_R)
+        clouds += [object[idx].detach(), data_dict["obj_init"][idx].detach()]
+        colors += [self.VIEW_RED, self.VIEW_YELLOW]
+        radii += [self.VIEW_POINT_R, self.VIEW_POINT_R]
+        hc, hcol, hr = self._human_clouds(data_dict, smpl_verts)
+        clouds, colors, radii = clouds + hc, colors + hcol, radii + hr
+        for key, colour in (("obj_center_pred", self.VIEW_CYAN), ("smpl_center_pred", self.VIEW_YELLOW),
+                            ("smpl_center_act", self.VIEW_MAGENTA)):
+            if key in data_dict:
+                clouds.append(data_dict[key][idx].detach().reshape(1, 3))
+                colors.append(colour)
+                radii.append(0.06)
+        return self._cloud_views(data_dict, smpl, clouds, colors, radii)
+
+    def _contact_view_data(self, data_dict, model, obj_center_pred, object, smpl, smpl_verts):
+        """what visualize_contact_fitting adds to data_dict for the whole batch: the contact masks (two field queries) and the
+        three centres; the network's query state is restored"""
+        kept = (model.preds, model.points, model.intermediate_preds_list)
+        try:
+            with torch.no_grad():
+                model.query(smpl_verts, **data_dict["query_dict"])
+                data_dict["contact_mask_h"] = model.get_preds()[0][:, 1, :] < 0.08
+                model.query(object, **data_dict["query_dict"])
+                data_dict["contact_mask_o"] = model.get_preds()[0][:, 0, :] < 0.08
+                J, _, _ = smpl.get_landmarks()
+                data_dict["obj_center_pred"] = obj_center_pred
+                data_dict["smpl_center_pred"] = data_dict["smpl_center"]
+                data_dict["smpl_center_act"] = J[:, 8]
+        finally:
+            model.preds, model.points, model.intermediate_preds_list = kept
+
+    def visualize_contact_fitting(self, data_dict, edges, image, model, obj_center_pred, object, smpl, smpl_verts):
+        """[:798-845] the contact masks from two field queries (at the SMPL vertices and at the object points, df < 0.08), the
+        three centres, then visualize_fitting; with `image` / `edges` (the silhouette phase's rendering and edge map, with
+        data_dict['image_ref'] / ['edt_ref']) the mask and edge panels are appended below.  Runs under no_grad and leaves
+        model.preds / points / intermediate_preds_list as it found them.  -> (512 [+ h], 1152, 3) uint8"""
+        idx = self._view_index
+        self._contact_view_data(data_dict, model, obj_center_pred, object, smpl, smpl_verts)
+        view = self.visualize_fitting(data_dict, object, smpl, smpl_verts)
+        if image is None or edges is None:
+            return view
+        u8 = lambda x: (x[idx].detach().float().cpu().numpy() * 255).astype(np.uint8)     # noqa: E731
+        img, img_ref, edt, edt_ref = u8(image), u8(data_dict["image_ref"]), u8(edges), u8(data_dict["edt_ref"])
+        h, w = img.shape[:2]
+        panels = np.zeros((h, max(2 * w, view.shape[1]), 3), np.uint8)
+        panels[:, :w, 0], panels[:, :w, 2] = img_ref, img               # red: the reference mask, blue: the rendering
+        panels[:, w:2 * w, 0], panels[:, w:2 * w, 2] = edt_ref, edt
+        if panels.shape[1] > view.shape[1]:
+            view = np.concatenate([view, np.zeros((view.shape[0], panels.shape[1] - view.shape[1], 3), np.uint8)], 1)
+        return np.concatenate([view, panels], 0)
+
+    def save_neural_recon(self, train_paths, recon_batch, save_name, tid):
+        """[:704-718] the dense point clouds of a batch, one k{tid}_densepc.npz per frame: a dict per target ('human',
+        'object') holding every entry of that target for the frame"""
+        files = []
+        for i, x in enumerate(train_paths):
+            seq, frame = str(x).split(os.sep)[-3], str(x).split(os.sep)[-2]
+            folder = os.path.join(self.outpath, seq, frame, save_name)
+            os.makedirs(folder, exist_ok=True)
+            out_dict = {}
+            for tar in recon_batch:
+                out_dict[tar] = {t: (v[i].detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v[i]))
+                                 for t, v in recon_batch[tar].items()}
+            files.append(os.path.join(folder, f"k{tid}_densepc.npz"))
+            np.savez(files[-1], **out_dict)
+        return files
+
+    # the debug files of a batch, written BETWEEN the phases of the optimisation (never inside a recorded step)
+    def _debug_files(self, image_paths, what):
+        save_name, tid = self.debug_dest
+        return [f.replace(".smpl.ply", f".debug_{what}.png") for f in self.get_output_paths(image_paths, save_name, tid)[0]]
+
+    def _debug_on(self):
+        return bool(self.debug) and self.outpath is not None and self.debug_dest is not None
+
+    def debug_after_smpl(self, prep, data_dict, smpl):
+        """after optimize_smpl: k{tid}.debug_smpl.png per frame and the dense clouds (save_neural_recon)"""
+        if not self._debug_on():
+            return
+        from ..utils.render_utils import write_png
+        paths = prep["data"]["path"]
+        self.save_neural_recon(paths, prep["pc"], *self.debug_dest)
+        model = prep["model"]
+        kept = (model.preds, model.points, model.intermediate_preds_list)
+        try:
+            with torch.no_grad():
+                smpl.forget()
+                verts = smpl()[0]
+                dd = dict(data_dict)
+                dd["smpl_center_pred"] = self.compute_smpl_center_pred(data_dict, model, smpl)
+                for i, f in enumerate(self._debug_files(paths, "smpl")):
+                    self._view_index = i
+                    write_png(f, self.visualize_smpl_fit(dd, smpl, verts))
+        finally:
+            self._view_index = 0
+            model.preds, model.points, model.intermediate_preds_list = kept
+            smpl.forget()
+
+    def debug_after_object(self, prep, data_dict, smpl, obj_R, obj_t, obj_s):
+        """after optimize_smpl_object: k{tid}.debug_object.png per frame"""
+        if not self._debug_on():
+            return
+        from ..utils.render_utils import write_png
+        paths, model = prep["data"]["path"], prep["model"]
+        kept = (model.preds, model.points, model.intermediate_preds_list)
+        try:
+            with torch.no_grad():
+                smpl.forget()
+                verts = smpl()[0]
+                dd = dict(data_dict)
+                if "smpl_center" not in dd:
+                    dd["smpl_center"] = self.compute_smpl_center_pred(data_dict, model, smpl)
+                object = self.transform_obj_verts(data_dict["objects"].detach(), self.decopose_axis(obj_R.detach(), no_rand=True),
+                                                  obj_t.detach(), obj_s.detach())
+                model.query(object, **data_dict["query_dict"])
+                obj_center_pred = dd["smpl_center"] + torch.mean(model.get_preds()[3][:, 3:, :], -1)
+                # what visualize_contact_fitting(dd, None, None, ...) draws, with the batch's queries made once for all frames
+                self._contact_view_data(dd, model, obj_center_pred, object, smpl, verts)
+                for i, f in enumerate(self._debug_files(paths, "object")):
+                    self._view_index = i
+                    write_png(f, self.visualize_fitting(dd, object, smpl, verts))
+        finally:
+            self._view_index = 0
+            model.preds, model.points, model.intermediate_preds_list = kept
+            smpl.forget()

@@ -249,39 +249,46 @@ class ReconFitterBehave(ReconFitterBase):
                                 obj_R=self.decopose_axis(obj_R, no_rand=True).detach(), obj_t=obj_t.detach(),
                                 obj_s=obj_s.detach()))
         use_pipe = self.pipeline if pipeline is None else pipeline
-        if use_pipe and len(todo) > 1 and torch.device(self.device).type == "cuda":
-            import sys
-            sw = os.environ.get("CHORE_PIPE_SWITCH_US")
-            old_sw = sys.getswitchinterval()
-            if sw:
-                sys.setswitchinterval(float(sw) * 1e-6)
-            try:
-                if self.batch_seed is None:            # two host threads cannot share the process-wide random streams
-                    self._pipe_seed = int(torch.initial_seed() % (1 << 31))
-                if os.environ.get("CHORE_PIPE_OWN_STREAM"):
-                    dev = torch.device(self.device)
-                    cur = torch.cuda.current_stream(dev)
-                    st = self.__dict__.get("_pipe_main")
-                    if st is None:
-                        st = self._pipe_main = torch.cuda.Stream(dev)
-                    st.wait_stream(cur)
-                    with torch.cuda.stream(st):
+        if self.debug:        # the debug views are written between the phases of a batch, by the serial loop (bit-equal to the others)
+            use_pipe = False
+            if save and self.outpath is not None:
+                self.debug_dest = (args.save_name, args.test_kid)
+        try:
+            if use_pipe and len(todo) > 1 and torch.device(self.device).type == "cuda":
+                import sys
+                sw = os.environ.get("CHORE_PIPE_SWITCH_US")
+                old_sw = sys.getswitchinterval()
+                if sw:
+                    sys.setswitchinterval(float(sw) * 1e-6)
+                try:
+                    if self.batch_seed is None:            # two host threads cannot share the process-wide random streams
+                        self._pipe_seed = int(torch.initial_seed() % (1 << 31))
+                    if os.environ.get("CHORE_PIPE_OWN_STREAM"):
+                        dev = torch.device(self.device)
+                        cur = torch.cuda.current_stream(dev)
+                        st = self.__dict__.get("_pipe_main")
+                        if st is None:
+                            st = self._pipe_main = torch.cuda.Stream(dev)
+                        st.wait_stream(cur)
+                        with torch.cuda.stream(st):
+                            self._fit_pipelined(todo, generator, finish)
+                        cur.wait_stream(st)
+                    elif use_pipe == "chains":
+                        self._fit_concurrent(todo, generator, finish)
+                    else:
                         self._fit_pipelined(todo, generator, finish)
-                    cur.wait_stream(st)
-                elif use_pipe == "chains":
-                    self._fit_concurrent(todo, generator, finish)
-                else:
-                    self._fit_pipelined(todo, generator, finish)
-            finally:
-                self._pipe_seed = None
-                sys.setswitchinterval(old_sw)
-        else:
-            for i, data in todo:
-                # (index only when per-batch generators are on: a subclass's fit_batch(data, generator) keeps working)
-                fitted = self.fit_batch(data, generator) if self.batch_seed is None else self.fit_batch(data, generator, index=i)
-                if self.batch_ends is not None and torch.device(self.device).type == "cuda":
-                    self._mark_read([None], 0, torch.cuda.current_stream(torch.device(self.device)))
-                finish(i, data, fitted)
+                finally:
+                    self._pipe_seed = None
+                    sys.setswitchinterval(old_sw)
+            else:
+                for i, data in todo:
+                    # (index only when per-batch generators are on: a subclass's fit_batch(data, generator) keeps working)
+                    fitted = self.fit_batch(data, generator) if self.batch_seed is None else self.fit_batch(data, generator, index=i)
+                    if self.batch_ends is not None and torch.device(self.device).type == "cuda":
+                        self._mark_read([None], 0, torch.cuda.current_stream(torch.device(self.device)))
+                    finish(i, data, fitted)
+        finally:
+            self.debug_dest = None      # a later fit_batch / fit_recon(save=False) must not write to this call's folders
         return results
 
     # Every batch's point-cloud random numbers from generators of its own (seed = batch_seed + the batch's index in the loader):
@@ -339,12 +346,16 @@ class ReconFitterBehave(ReconFitterBase):
          smpl) = prep["smplfit"]
         smpl, scale = self.optimize_smpl(smpl, betas_dict, **(smpl_iters or self.smpl_iters or dict(iter_for_kpts=1, iter_for_pose=1,
                                                                                                     iter_for_betas=1)))
+        if self.debug:
+            self.debug_after_smpl(prep, betas_dict, smpl)
         obj_R, obj_s, obj_t, object_init = self.init_obj_fit_data(batch_size, human_t, pc_generated, scale)
         data_dict = {"obj_R": obj_R, "obj_t": obj_t, "obj_s": obj_s, "objects": object_init, "smpl": smpl,
                      "images": data.get("images").to(self.device), "human_init": human_points, "obj_init": obj_points,
                      "human_parts": human_parts, "part_labels": part_labels, "part_colors": part_colors,
                      "body_kpts": body_kpts, "query_dict": query_dict, "obj_t_init": obj_t.clone().detach().to(self.device)}
         smpl, obj_R, obj_t = self.optimize_smpl_object(prep["model"], data_dict, **(object_iters or self.object_iters or {}))
+        if self.debug:
+            self.debug_after_object(prep, data_dict, smpl, obj_R, obj_t, obj_s)
         return smpl, obj_R, obj_t, obj_s
 
     def fit_batch(self, data, generator, smpl_iters=None, object_iters=None, index=None):

@@ -137,6 +137,69 @@ def rasterize_rgbad(faces, textures, light=None, image_size=256, anti_aliasing=T
     return out
 
 
+def splat_points(points_ndc, colors=None, radius=2.0, image_size=256, anti_aliasing=True, near=DEFAULT_NEAR, far=DEFAULT_FAR,
+                 ambient=0.6, background_color=(0, 0, 0), return_index=False):
+    """point clouds as shaded discs in one call (chore_splat_fwd; the rule is written down in include/chore_hip.h):
+    points_ndc (B,N,3) projected points [u, v in [-1,1], depth] as `Renderer.transform` returns them, colors (B,N,3) or None =
+    white, radius in output pixels: a number or (B,N)
+    -> dict(rgb (B,3,S,S), depth (B,S,S), alpha (B,S,S)[, point_index (B,S*ssaa,S*ssaa) int32, rows not flipped]).
+    The nearest point wins a sample, then the smallest index, whatever the order of the points.  Inputs are detached;
+    N == 0 gives the background."""
+    if not points_ndc.is_cuda:
+        raise RuntimeError("chore_amd needs device tensors (no CPU path)")
+    dev = points_ndc.device
+    pts = points_ndc.detach().float().contiguous()
+    if pts.dim() != 3 or pts.shape[2] != 3:
+        raise ValueError("points_ndc (B,N,3) expected, got %s" % (tuple(pts.shape),))
+    B, N = pts.shape[:2]
+    ssaa, S = (2 if anti_aliasing else 1), int(image_size)
+    col = None
+    if colors is not None:
+        col = colors.detach().to(dev).float().contiguous()
+        if tuple(col.shape) != (B, N, 3):
+            raise ValueError("colors (B,N,3) expected, got %s" % (tuple(col.shape),))
+    rad, radius_px = None, 0.0
+    if torch.is_tensor(radius) and radius.dim() > 0:
+        rad = radius.detach().to(dev).float().contiguous()
+        if tuple(rad.shape) != (B, N):
+            raise ValueError("radius: a number or (B,N) expected, got %s" % (tuple(rad.shape),))
+    else:
+        radius_px = float(radius)
+    if N == 0:
+        bgc = torch.tensor([float(c) for c in background_color], dtype=torch.float32, device=dev)
+        out = {"rgb": bgc.view(1, 3, 1, 1).expand(B, 3, S, S).contiguous(),
+               "depth": torch.full((B, S, S), float(far), dtype=torch.float32, device=dev),
+               "alpha": torch.zeros(B, S, S, dtype=torch.float32, device=dev)}
+        if return_index:
+            out["point_index"] = torch.full((B, S * ssaa, S * ssaa), -1, dtype=torch.int32, device=dev)
+        return out
+    h = _lib.handle(dev.index or 0)
+    nbytes = _lib.lib.chore_splat_workspace_bytes(B, N, S, ssaa)
+    if nbytes == 0:
+        raise ValueError("unsupported splat shape B=%d N=%d image_size=%d ssaa=%d" % (B, N, S, ssaa))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    rgb = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
+    depth = torch.empty(B, S, S, dtype=torch.float32, device=dev)
+    alpha = torch.empty(B, S, S, dtype=torch.float32, device=dev)
+    pim = torch.empty(B, S * ssaa, S * ssaa, dtype=torch.int32, device=dev) if return_index else None
+    bg = (ctypes.c_float * 3)(*[float(c) for c in background_color])
+    _lib.check(_lib.lib.chore_splat_fwd(h, pts.data_ptr(), col.data_ptr() if col is not None else None,
+                                        rad.data_ptr() if rad is not None else None, radius_px, B, N, S, ssaa, float(ambient),
+                                        float(near), float(far), bg, rgb.data_ptr(), depth.data_ptr(), alpha.data_ptr(),
+                                        pim.data_ptr() if return_index else None, ws.data_ptr(),
+                                        torch.cuda.current_stream(dev).cuda_stream), h, "chore_splat_fwd")
+    out = {"rgb": rgb, "depth": depth, "alpha": alpha}
+    if return_index:
+        out["point_index"] = pim
+    return out
+
+
+def world_radius_to_pixels(world_radius, z, focal_px):
+    """pixel radius of a sphere of `world_radius` metres at depth z under a focal length of `focal_px` OUTPUT pixels:
+    focal_px * world_radius / z, so points shrink with distance"""
+    return focal_px * world_radius / z
+
+
 class Renderer(nn.Module):
     """neural_renderer.Renderer (renderer.py:11-63): same constructor arguments and attributes.  K / R / t may live on any
     device; they are moved to the vertices' device when rendering."""
@@ -234,3 +297,31 @@ class Renderer(nn.Module):
 
     def render_silhouettes(self, vertices, faces, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
         return self._rasterize(vertices, faces, None, (K, R, t, dist_coeffs, orig_size))["alpha"]
+
+    def focal_pixels(self, K=None, orig_size=None):
+        """focal length in pixels of THIS renderer's output: K[0,0] scaled from `orig_size` to image_size in projection
+        mode ((B,) tensor or a number), (image_size / 2) / tan(viewing_angle) in look_at mode (perspective() divides by
+        tan(angle) and the normalised half-width 1 is image_size / 2 pixels)"""
+        if self.camera_mode == "projection":
+            K = self.K if K is None else K
+            orig_size = self.orig_size if orig_size is None else orig_size
+            fx = torch.as_tensor(K, dtype=torch.float32).reshape(-1, 3, 3)[:, 0, 0]
+            return fx * (self.image_size / float(orig_size))
+        return 0.5 * self.image_size / math.tan(math.radians(self.viewing_angle))
+
+    def render_points(self, points, colors=None, radius=2.0, world_radius=None, K=None, R=None, t=None, dist_coeffs=None,
+                      orig_size=None):
+        """world points (B,N,3) as shaded discs -> (rgb (B,3,S,S), depth (B,S,S), alpha (B,S,S)); inputs are detached.
+        radius: output pixels, a number or (B,N).  world_radius (metres, a number or (B,N)) replaces it by the per-point
+        pixel radius focal_px * world_radius / z."""
+        points = points.detach().float()
+        ndc = self.transform(points, K, R, t, dist_coeffs, orig_size)
+        if world_radius is not None:
+            focal = self.focal_pixels(K, orig_size)
+            if torch.is_tensor(focal):
+                focal = focal.to(ndc.device).view(-1, 1)
+            wr = torch.as_tensor(world_radius, dtype=torch.float32).to(ndc.device)
+            radius = world_radius_to_pixels(wr, ndc[:, :, 2], focal).expand(ndc.shape[0], ndc.shape[1])
+        out = splat_points(ndc, colors, radius, self.image_size, self.anti_aliasing, self.near, self.far,
+                           background_color=self.background_color)
+        return out["rgb"], out["depth"], out["alpha"]

@@ -13,11 +13,15 @@ nothing in the checkout calls.
 IO stays with the caller).
 """
 import os
+import struct
+import zlib
 
 import numpy as np
 import torch
 
 from .. import render as nr
+from ..model.camera import KinectColorCamera
+from ..recon.recon_fit_base import MTURK_COLORS
 
 SMPL_OBJ_COLOR_LIST = [
     [0.65098039, 0.74117647, 0.85882353],      # body
@@ -30,6 +34,24 @@ KINECT_FOCAL = (979.784, 979.840)
 KINECT_CENTRE = (1018.952, 779.486)
 MEAN_CROP_CENTER = (1008, 995)                 # where the in-the-wild loader moves every crop centre to
 _FLIP_Y = np.array([1.0, -1.0, 1.0])           # look_at views have y up, the Kinect camera has y down
+PART_COLORS = MTURK_COLORS                      # the fitter's 14 body-part colours, rows in [0,1]
+CLOUD_VIEW_SIZE, CLOUD_SIDE_SIZE = 512, 640    # render_cloud_views: the input view and the side view, pixels
+
+
+def write_png(path, u8):
+    """an (H,W,3) RGB or (H,W) / (H,W,1) grey uint8 array as an 8-bit PNG, with zlib and struct only"""
+    a = np.ascontiguousarray(u8)
+    if a.dtype != np.uint8 or a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] not in (1, 3)) or a.size == 0:
+        raise ValueError("write_png takes a non-empty uint8 array (H,W), (H,W,1) or (H,W,3), got %s %s" % (a.dtype, a.shape))
+    h, w = a.shape[:2]
+    colour_type = 2 if a.ndim == 3 and a.shape[2] == 3 else 0
+    rows = np.concatenate([np.zeros((h, 1), np.uint8), a.reshape(h, -1)], axis=1)          # filter type 0 on every row
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xffffffff)
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, colour_type, 0, 0, 0)) +
+                chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + chunk(b"IEND", b""))
 
 
 class Mesh:
@@ -143,6 +165,14 @@ class NrWrapper:
         all_faces, textures = get_faces_and_textures(verts, faces, colors_list=[c for _, c in pairs])
         return torch.cat(verts, dim=1), all_faces, textures
 
+    def render_points(self, renderer, clouds, colors, world_radius):
+        """several point clouds in ONE splat call, so that occlusion between them is resolved per sample and nothing has to
+        be composited: clouds [(N_i,3) world points], colors [one (3,) colour or (N_i,3) per cloud], world_radius metres, one
+        number for all or one per cloud.  -> image (S,S,3) float in [0,1], coverage (S,S) float in [0,1]"""
+        pts, col, rad = concat_clouds(clouds, colors, world_radius, self.device)
+        rgb, _, alpha = renderer.render_points(pts[None], col[None], world_radius=rad[None])
+        return rgb[0].permute(1, 2, 0).clamp(0, 1).cpu().numpy(), alpha[0].cpu().numpy()
+
     def prepare_side_rend(self, meshes, maxd=1.5, colors=None):
         """tensors for setup_side_renderer: y flipped, scaled so that the bounding box measures `maxd`, centred at the
         vertex mean.  The caller's meshes are not modified.  -> faces, textures, vertices"""
@@ -171,6 +201,80 @@ class NrWrapper:
         if hasattr(mesh, 'vc'):
             twin.vc = np.array(mesh.vc)
         return twin
+
+
+def concat_clouds(clouds, colors, radii, device):
+    """clouds [(N_i,3)], colors [(3,) or (N_i,3)], radii a number or one per cloud -> points (N,3), colours (N,3), radii (N,)
+    float32 tensors on `device`, cloud after cloud (tensors already there are not copied through the host)"""
+    if not isinstance(radii, (list, tuple)):
+        radii = [radii] * len(clouds)
+    on = lambda x: torch.as_tensor(x, dtype=torch.float32, device=device) if not torch.is_tensor(x) else \
+        x.detach().to(device=device, dtype=torch.float32)                  # noqa: E731
+    pts, col, rad = [], [], []
+    for p, c, r in zip(clouds, colors, radii):
+        p, c = on(p).reshape(-1, 3), on(c)
+        pts.append(p)
+        col.append(c.reshape(1, 3).expand(len(p), 3) if c.numel() == 3 else c.reshape(len(p), 3))
+        rad.append(torch.full((len(p),), float(r), device=device))
+    return torch.cat(pts), torch.cat(col), torch.cat(rad)
+
+
+def render_cloud_views(images_b, crop_center_b, clouds, colors, radii, markers2d=None, side_renderer=None, camera=None,
+                       maxd=1.5, min_radius_px=1.0):
+    """the fitter's point clouds of ONE frame in two views -> (512, 512 + 640, 3) uint8.
+
+    images_b (C,H,W) network input of the frame (channels 0..2 RGB in [0,1]), crop_center_b (2,), clouds / colors / radii as
+    `concat_clouds` takes them (camera-space points, world radii in metres), markers2d [(xy (M,2) pixel positions in the 512-px
+    network input, colour (3,), radius in pixels)].
+    Input view (left, 512 px): the clouds through the network's own camera -- `camera.project_points` gives [nx, ny, z] and
+    the splats take v = -ny, since the rasterisers' output rows are flipped -- alpha-blended over the input photo; the
+    markers are splats at a depth just inside `near`, so they win every sample they cover.
+    Side view (right, the middle 512 rows of a 640-px rendering): the same clouds through setup_side_renderer(2.0, 0., 90.) after
+    the y-flip, scaling (bounding box -> `maxd`) and centring of NrWrapper.prepare_side_rend.
+    No disc is drawn smaller than `min_radius_px`: a scattered cloud scales the side view down, and points must not vanish."""
+    dev = images_b.device
+    camera = KinectColorCamera() if camera is None else camera
+    pts, col, rad = concat_clouds(clouds, colors, radii, dev)
+    S, near = CLOUD_VIEW_SIZE, nr.renderer.DEFAULT_NEAR
+    proj = camera.project_points(pts[None], crop_center_b.to(dev).float().reshape(1, 2)).transpose(1, 2)     # (1,N,3)
+    ndc = torch.stack([proj[..., 0], -proj[..., 1], proj[..., 2]], dim=-1)
+    focal = camera.fx_px * S / camera.crop_size
+    rad_px = nr.world_radius_to_pixels(rad[None], ndc[..., 2], focal).clamp(min=min_radius_px)
+    if markers2d:
+        for xy, c, r in markers2d:
+            xy = torch.as_tensor(np.asarray(xy.detach().cpu()) if torch.is_tensor(xy) else np.asarray(xy), dtype=torch.float32)
+            xy = xy.reshape(-1, 2).to(dev)
+            u, v = (2 * xy[:, 0] + 1) / S - 1, -((2 * xy[:, 1] + 1) / S - 1)
+            ndc = torch.cat([ndc, torch.stack([u, v, torch.full_like(u, near * 1.01)], -1)[None]], 1)
+            col = torch.cat([col, torch.tensor(c, dtype=torch.float32, device=dev).reshape(1, 3).expand(len(xy), 3)])
+            rad_px = torch.cat([rad_px, torch.full((1, len(xy)), float(r), device=dev)], 1)
+    out = nr.splat_points(ndc, col[None], rad_px, S, True, near, nr.renderer.DEFAULT_FAR, ambient=0.6)
+    photo = images_b[:3].detach().float().clamp(0, 1)
+    if photo.shape[1] != S or photo.shape[2] != S:         # nearest-neighbour to the view's size
+        iy = (torch.arange(S, device=dev) * photo.shape[1]) // S
+        ix = (torch.arange(S, device=dev) * photo.shape[2]) // S
+        photo = photo[:, iy][:, :, ix]
+    front = out["rgb"][0] + (1 - out["alpha"][0])[None] * photo        # the splat colours are weighted by their coverage already
+    front = (front.permute(1, 2, 0).clamp(0, 1) * 255).to(torch.uint8).cpu().numpy()
+
+    side_renderer = setup_side_renderer(2.0, 0., 90.) if side_renderer is None else side_renderer
+    n = len(pts)
+    # prepare_side_rend on the device: y flipped, the bounding box scaled to `maxd` (cal_norm_scale), centred at the mean
+    flipped = pts * torch.tensor(_FLIP_Y, dtype=torch.float32, device=dev)
+    keep = torch.isfinite(flipped).all(dim=1, keepdim=True)
+    big = torch.finfo(torch.float32).max
+    extent = torch.where(keep, flipped, -big).amax(0) - torch.where(keep, flipped, big).amin(0)
+    scale = (maxd / extent.clamp(min=1e-12)).min()
+    mean = torch.where(keep, flipped, 0.0).sum(0) / keep.sum().clamp(min=1)
+    centred = scale * (flipped - mean)
+    side_ndc = side_renderer.transform(centred[None])
+    side_px = nr.world_radius_to_pixels((rad * scale)[None], side_ndc[..., 2], side_renderer.focal_pixels())
+    rgb = nr.splat_points(side_ndc, col[None, :n], side_px.clamp(min=min_radius_px), side_renderer.image_size,
+                          side_renderer.anti_aliasing, side_renderer.near, side_renderer.far,
+                          background_color=side_renderer.background_color)["rgb"]
+    side = (rgb[0].permute(1, 2, 0).clamp(0, 1) * 255).to(torch.uint8).cpu().numpy()
+    top = (side.shape[0] - S) // 2
+    return np.concatenate([front, side[top:top + S]], axis=1)
 
 
 def _resize_u8(img, dsize, device):

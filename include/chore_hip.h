@@ -335,6 +335,34 @@ int chore_render_fwd(chore_handle* h, const float* tri, const float* textures, c
                      float* depth, float* alpha, int* sample_face_index, void* workspace, chore_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Point clouds as shaded discs, forward only  (what the reference's -d viewer shows, recon/recon_fit_base.py:442-511,
+ * 749-845, is all point clouds; there is no counterpart kernel in the reference, the rule below is this library's own).
+ * pts (B,N,3) projected points [u, v in [-1,1], depth], the layout of chore_render_fwd's triangle vertices; rgb_in (B,N,3)
+ * or NULL = white; radius (B,N) in OUTPUT pixels or NULL = radius_px for every point; ambient in [0,1]; background3: HOST,
+ * 3 floats; ssaa 1 or 2; size * ssaa <= 4096; B, N >= 1.  Sample grid S = size * ssaa, all arithmetic fp32, each operation
+ * rounded once (no contraction), in the association written here:
+ *   - point n is skipped if u, v, z or r is NaN, if r <= 0, or if z <= near_z || far_z <= z (chore_render_fwd's depth test);
+ *   - rs = fminf(r * ssaa, 64): larger radii are clamped, not refused;
+ *   - px = 0.5f * ((u * S + S) - 1.0f), py alike from v: where chore_render_fwd puts a vertex at the same [u, v];
+ *   - sample (column i, row j) is covered iff dx*dx + dy*dy <= rs*rs with dx = (float)i - px, dy = (float)j - py;
+ *   - the winner of a sample is the covering point with the smallest z, then the smallest n, whatever the order of the
+ *     points (a 64-bit integer atomicMin per sample: no float atomics, bit-equal across calls, permutations and replays);
+ *   - colour = rgb_in[n] * (ambient + (1 - ambient) * sqrtf(fmaxf(0, 1 - d2 / (rs*rs)))), depth = z, alpha = 1; an empty
+ *     sample is background3 / far_z / 0.
+ * Outputs are resolved as chore_render_fwd's: row r holds the sample rows of block size-1-r, the mean over the
+ * ssaa x ssaa samples for rgb (B,3,size,size), depth (B,size,size) and alpha (B,size,size) alike.  sample_point_index
+ * (B,size*ssaa,size*ssaa) int32 or NULL: the winner of every sample, -1 = none, rows NOT flipped.
+ * workspace: chore_splat_workspace_bytes(B, N, size, ssaa) bytes, 16-byte aligned (0 = unsupported shape); it depends on the
+ * shapes only, nothing is allocated and no device value is read by the host, so the call can be captured into a graph.
+ * CHORE_EINVAL, before anything is launched: a NULL pts / background3 / output / workspace, N < 1, B < 1, ssaa not 1 or 2,
+ * size * ssaa > 4096, ambient outside [0,1], near_z >= far_z, radius == NULL with radius_px <= 0.
+ * ------------------------------------------------------------------------------------------- */
+size_t chore_splat_workspace_bytes(int B, int N, int size, int ssaa);
+int chore_splat_fwd(chore_handle* h, const float* pts, const float* rgb_in, const float* radius, float radius_px, int B, int N,
+                    int size, int ssaa, float ambient, float near_z, float far_z, const float* background3, float* rgb,
+                    float* depth, float* alpha, int* sample_point_index, void* workspace, chore_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Evaluation metrics, fp64  (replace recon/eval/chamfer_distance.py:10-52 = sklearn kd-tree nearest neighbours, and
  * recon/eval/pose_utils.py compute_transform :145-180 / compute_similarity_transform :103-143).
  *   chore_eval_chamfer   out[0] = mean_i min_j |x_i - y_j| (direction 'x_to_y'), out[1] = the other direction
