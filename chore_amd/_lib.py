@@ -94,6 +94,9 @@ SIGNATURES = {
                                   c_void_p]),
     "chore_conv2d_fwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "chore_conv2d_pool_fwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p]),
     "chore_amax_bytes": (c_size_t, []),
     "chore_absmax_f32": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     "chore_conv2d_bwd_data": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int,
@@ -145,6 +148,9 @@ SIGNATURES = {
     "chore_stem_workspace_bytes": (c_size_t, [c_int]),
     "chore_stem_fwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_void_p]),
+    "chore_stem_x3_workspace_bytes": (c_size_t, [c_int]),
+    "chore_stem_x3_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p]),
     "chore_stem_wgrad_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "chore_stem_bwd_weight": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p]),

@@ -33,7 +33,7 @@ struct chore_handle {
 };
 // kernel families and flag bits of chore_handle::last_conv (include/chore_hip.h, chore_debug_last_conv)
 enum { CONV_FAM_LDS = 1, CONV_FAM_SMALL = 2, CONV_FAM_PC = 3, CONV_FAM_MW = 4, CONV_FAM_RW = 5 };
-enum { CONV_FLAG_SCALED = 1, CONV_FLAG_GN = 2, CONV_FLAG_SMALL_GRID = 4, CONV_FLAG_RES = 8 };
+enum { CONV_FLAG_SCALED = 1, CONV_FLAG_GN = 2, CONV_FLAG_SMALL_GRID = 4, CONV_FLAG_RES = 8, CONV_FLAG_POOL = 16 };
 inline void chore_note_conv(chore_handle* h, int family, int rows, int nt, int tps, int nslot, int flags, int cin) {
     int* r = h->last_conv;
     r[0] = family; r[1] = rows; r[2] = nt; r[3] = tps; r[4] = nslot; r[5] = flags; r[6] = cin; ++r[7];

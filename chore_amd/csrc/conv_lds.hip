@@ -549,6 +549,10 @@ ConvPlan conv_plan(int dtype, int taps, int B, int H, int W, int Cin, int Cout) 
     return ConvPlan{nt, TH, tiles_of(H, W), tps, 0};
 }
 
+bool conv_pool_covers(int dtype, int taps, int Cin, int Cout, int H, int W) {
+    return conv_use_pc() && conv_mw_pool_covers(dtype, taps, Cin, Cout, H, W);
+}
+
 int launch_conv(chore_handle* h, int dtype, int taps, const ConvArgs& a_in, hipStream_t s) {
     const int cc = dtype == CHORE_F32 ? 16 : 32;
     if (dtype != CHORE_F32 && dtype != CHORE_BF16 && dtype != CHORE_F16X3 && dtype != CHORE_F16) CHORE_FAIL(h, CHORE_EINVAL, "conv: bad dtype");
@@ -561,6 +565,15 @@ int launch_conv(chore_handle* h, int dtype, int taps, const ConvArgs& a_in, hipS
         if (c % GN_GROUPS || gs > 8 || (gs & (gs - 1)))
             CHORE_FAIL(h, CHORE_EINVAL, "conv: GroupNorm over %d channels unsupported (group size must be 1, 2, 4 or 8)", c);
     }
+    if (a_in.pool.p) {   // a pooled output rides in conv_mw_kernel's epilogue only: the caller asked conv_pool_covers() first
+        const PcPlan mp = conv_mw_plan(dtype, taps, a_in.B, a_in.H, a_in.W, a_in.in.C, a_in.Cout, a_in.fill);
+        if (a_in.st_pool && (a_in.st_pool_C % GN_GROUPS || a_in.st_pool_C / GN_GROUPS > 8 || ((a_in.st_pool_C / GN_GROUPS) & (a_in.st_pool_C / GN_GROUPS - 1))))
+            CHORE_FAIL(h, CHORE_EINVAL, "conv: GroupNorm over %d channels unsupported (group size must be 1, 2, 4 or 8)", a_in.st_pool_C);
+        if (!conv_pool_covers(dtype, taps, a_in.in.C, a_in.Cout, a_in.H, a_in.W) || !mp.th || !conv_mw_covers(dtype, taps, mp, a_in))
+            CHORE_FAIL(h, CHORE_EINVAL, "conv: this launch cannot carry a pooled output (taps=%d Cin=%d Cout=%d %dx%d)", taps, a_in.in.C, a_in.Cout, a_in.H, a_in.W);
+        return launch_conv_mw(h, dtype, taps, mp, a_in, s);
+    }
+    if (!a_in.out.p) CHORE_FAIL(h, CHORE_EINVAL, "conv: no output");
     if (conv_mw_on(dtype, taps) && conv_mw_fill(a_in.fill) < 256 && !a_in.res2.p) {      // the small maps on dense conv_mw tiles (conv_mw_plan)
         const PcPlan mp = conv_mw_plan(dtype, taps, a_in.B, a_in.H, a_in.W, a_in.in.C, a_in.Cout, a_in.fill);
         if (mp.th && conv_mw_covers(dtype, taps, mp, a_in)) return launch_conv_mw(h, dtype, taps, mp, a_in, s);

@@ -67,8 +67,19 @@ template <int TAPS, int TH_, int NT_, int TPS_, int NSLOT_, bool X3_, int WPL_> 
     static constexpr int NU = TH * PTW * G8 / MWT;                  // (pixel, 8 channels) units per thread in the epilogue
     static constexpr bool CROSS = NSLOT >= 3 && KROWS > 1;          // next K-step's first fragments requested before the barrier
     static constexpr size_t main_bytes(int Cin) { return (size_t)2 * PATCHB + (size_t)NSLOT * SBYTES + (size_t)Cin * 8 + 16; }
+    // the statistics reduction of the epilogue: `kinds` sums per channel (sum / sum of squares of raw and out: 4; + the pooled output: 6),
+    // every thread parks kinds x 8 partials as a row segment of part[NROW][kinds * NT], the columns are added into red[NSEG][kinds * NT].
+    // NSEG (segments of rows a column is added up in) does not depend on `kinds`: the sums of raw and out are formed in the same order
+    // with and without a pooled output, so folding the pooling moves no bit of them
+    static constexpr int NROW = MWT / G8;
+    static constexpr int NSEG = 4 * NT >= MWT ? 1 : MWT / (4 * NT);
+    static constexpr size_t stat_bytes(int kinds) { return (size_t)(NROW + NSEG) * kinds * NT * 4; }
+    static constexpr size_t scr_bytes() { return (size_t)TH * PTW * SCR_LD * 4; }
     static constexpr size_t epi_bytes() {
-        return (size_t)TH * PTW * SCR_LD * 4 > (size_t)(MWT * 32 + 4 * NT) * 4 ? (size_t)TH * PTW * SCR_LD * 4 : (size_t)(MWT * 32 + 4 * NT) * 4;
+        size_t m = scr_bytes();
+        if (stat_bytes(4) > m) m = stat_bytes(4);
+        if (stat_bytes(6) > m) m = stat_bytes(6);
+        return m;
     }
     static size_t smem_bytes(int Cin) { return main_bytes(Cin) > epi_bytes() ? main_bytes(Cin) : epi_bytes(); }
     static_assert(MB >= 1 && WAVES_M * MB == TH, "tile rows must divide over the waves");
@@ -109,7 +120,9 @@ __device__ __forceinline__ void wg_barrier_mw() {
 
 // GN: GroupNorm + ReLU fused into the staging (ConvArgs::in_st); SC (fp16 x 3 only): the input is a gradient whose range comes in
 // ConvArgs::in_amax (training's data-gradient convolutions)
-template <typename T, int TAPS, int TH_, int NT_, int TPS_, int NSLOT_, bool GN, bool SC>
+// POOL: the launch carries a pooled output (ConvArgs::pool).  A template parameter, not a runtime branch: the instantiations without it
+// compile none of the pooled epilogue and measure equal to round 6's on the dominant layer (profiles/r07_pool_fold.txt, section 2)
+template <typename T, int TAPS, int TH_, int NT_, int TPS_, int NSLOT_, bool GN, bool SC, bool POOL = false>
 __global__ __launch_bounds__(MWT, 1) void conv_mw_kernel(ConvArgs a) {
     if constexpr (IS_X3<T> || IS_H16<T>) f16_saturate_mode();     // the fp16 x 3 / fp16 operand split never produces inf (common.h)
     constexpr bool BF = std::is_same<T, bf16_t>::value;
@@ -543,10 +556,12 @@ __global__ __launch_bounds__(MWT, 1) void conv_mw_kernel(ConvArgs a) {
     wg_barrier_mw();
     MWSTAMP(3);
 
-    ST* out_p = (ST*)a.out.p + img * a.out.cs + a.out.co + nv;
+    static_assert(!POOL || (IS_X3<T> && !SC), "the pooled output: fp32 tensors of the forward pass");
+    ST* out_p = (!POOL || a.out.p) ? (ST*)a.out.p + img * a.out.cs + a.out.co + nv : nullptr;    // null (POOL only): only the pooled output is wanted
     ST* raw_p = a.raw.p ? (ST*)a.raw.p + img * a.raw.cs + a.raw.co + nv : nullptr;
     using ET = typename std::conditional<X3, float, typename std::conditional<BF, bf16_t, h16_t>::type>::type;       // store8 / load8 element tag
-    const bool want_stats = a.st_raw || a.st_out;
+    constexpr bool do_pool = POOL;     // 2x2 average of `out` stored beside it (ConvArgs::pool)
+    const bool want_stats = a.st_raw || a.st_out || (do_pool && a.st_pool);
     // statistics partials as register pairs (v_pk_add_f32 / v_pk_fma_f32): sum and sum of squares of what is stored
     f32x2 sr[4], qr[4], so[4], qo[4];
 #pragma unroll
@@ -588,7 +603,11 @@ __global__ __launch_bounds__(MWT, 1) void conv_mw_kernel(ConvArgs a) {
                     }
                 }
             }
-            store8<ET>((ET*)(out_p + pix * a.out.cs), f);
+            if (!POOL || out_p) store8<ET>((ET*)(out_p + pix * a.out.cs), f);
+            if constexpr (POOL) {      // the values as stored go back into this thread's own cell of the tile image
+                *(f32x4*)(scr + p * SCR_LD + g8 * 8) = f32x4{f[0], f[1], f[2], f[3]};
+                *(f32x4*)(scr + p * SCR_LD + g8 * 8 + 4) = f32x4{f[4], f[5], f[6], f[7]};
+            }
             if (want_stats) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -600,13 +619,55 @@ __global__ __launch_bounds__(MWT, 1) void conv_mw_kernel(ConvArgs a) {
         }
     }
 
+    // ---- pooled output: 2x2 windows never straddle a tile (TH even, 32 columns; H and W even), so a quarter of the (pixel, 8 channels)
+    //      units average four cells of the tile image: (((a + b) + c) + d) * 0.25f in PoolOp::column's order (enc_misc.hip) -- the
+    //      tensor the pooling pass would write, bit for bit
+    f32x2 sp[4], qp[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) sp[e] = qp[e] = f32x2{0.f, 0.f};
+    if constexpr (POOL) {
+        {
+            wg_barrier_mw();                                   // every cell holds its stored value
+            constexpr int NPU = (TH / 2) * (PTW / 2) * G8, NPJ = (NPU + MWT - 1) / MWT;
+            static_assert(TH % 2 == 0 && MWT % G8 == 0, "pooled units: whole windows per tile, a thread keeps its channels");
+            const int OH = a.H >> 1, OW = a.W >> 1;
+            float* pool_p = (float*)a.pool.p + (size_t)b * OH * OW * a.pool.cs + a.pool.co + nv;
+#pragma unroll
+            for (int j = 0; j < NPJ; ++j) {
+                const int pu = tid + MWT * j;                  // pu % G8 == g8
+                const int pp = pu / G8, py = pp / (PTW / 2), pxx = pp % (PTW / 2);
+                const int oy = (ty0 >> 1) + py, ox = (tx0 >> 1) + pxx;
+                if (pu < NPU && oy < OH && ox < OW) {
+                    const float* c0 = scr + ((2 * py) * PTW + 2 * pxx) * SCR_LD + g8 * 8;
+                    float v[8];
+#pragma unroll
+                    for (int hv = 0; hv < 2; ++hv) {
+                        const f32x4 va = *(const f32x4*)(c0 + 4 * hv), vb = *(const f32x4*)(c0 + SCR_LD + 4 * hv);
+                        const f32x4 vc = *(const f32x4*)(c0 + PTW * SCR_LD + 4 * hv), vd = *(const f32x4*)(c0 + (PTW + 1) * SCR_LD + 4 * hv);
+                        const f32x4 r = (((va + vb) + vc) + vd) * 0.25f;
+                        v[4 * hv] = r[0]; v[4 * hv + 1] = r[1]; v[4 * hv + 2] = r[2]; v[4 * hv + 3] = r[3];
+                    }
+                    store8<float>(pool_p + ((size_t)oy * OW + ox) * a.pool.cs, v);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const f32x2 t = {v[2 * e], v[2 * e + 1]};
+                        sp[e] += t;
+                        qp[e] = __builtin_elementwise_fma(t, t, qp[e]);
+                    }
+                }
+            }
+        }
+    }
+
     MWSTAMP(4);
-    if (want_stats) {   // uniform over the grid
-        // 256 threads x (4 sums x 8 channels) -> per-channel totals through LDS, in a fixed order: every thread parks its 32 partial
-        // sums as a row segment of part[thread / G8][kind * NT + channel]; the columns are added up by all threads (a column per
-        // thread and pass), the GroupNorm groups by one wave
-        constexpr int RL = 4 * NT, NROW = MWT / G8, NSEG = RL >= MWT ? 1 : MWT / RL, RPSEG = NROW / NSEG;
+    // 256 threads x (KINDS sums x 8 channels) -> per-channel totals through LDS, in a fixed order: every thread parks its partial
+    // sums as a row segment of part[thread / G8][kind * NT + channel]; the columns are added up by all threads (a column per
+    // thread and pass), the GroupNorm groups by one wave.  KINDS = 4: raw and out; 6: + the pooled output
+    auto reduce_stats = [&](auto kinds_t) {
+        constexpr int KINDS = decltype(kinds_t)::value;
+        constexpr int RL = KINDS * NT, NROW = G::NROW, NSEG = G::NSEG, RPSEG = NROW / NSEG;
         static_assert(RPSEG * NSEG == NROW, "statistics reduction geometry");
+        static_assert((size_t)(NROW + NSEG) * RL * 4 <= G::epi_bytes(), "statistics reduction scratch");
         wg_barrier_mw();                                       // every thread is done with the tile image
         float* part = (float*)smem;                            // [NROW][RL]
         float* red = part + NROW * RL;                         // [NSEG][RL]
@@ -617,6 +678,7 @@ __global__ __launch_bounds__(MWT, 1) void conv_mw_kernel(ConvArgs a) {
                 *(f32x4*)(q + 4) = f32x4{v[2][0], v[2][1], v[3][0], v[3][1]};
             };
             park(pr, sr); park(pr + NT, qr); park(pr + 2 * NT, so); park(pr + 3 * NT, qo);
+            if constexpr (KINDS == 6) { park(pr + 4 * NT, sp); park(pr + 5 * NT, qp); }
         }
         wg_barrier_mw();
         for (int cs = tid; cs < NSEG * RL; cs += MWT) {
@@ -629,14 +691,15 @@ __global__ __launch_bounds__(MWT, 1) void conv_mw_kernel(ConvArgs a) {
         }
         wg_barrier_mw();
         if (tid < NT) {
-            // thread = channel; kinds 0 / 1 = sum / sum of squares of `raw`, 2 / 3 of `out`.  All adds of the workgroup leave from ONE
-            // wave per 64 channels (per tensor: the group's sum from its first lane, the sum of squares from its second)
+            // thread = channel; kinds 0 / 1 = sum / sum of squares of `raw`, 2 / 3 of `out`, 4 / 5 of `pool`.  All adds of the workgroup
+            // leave from ONE wave per 64 channels (per tensor: the group's sum from its first lane, the sum of squares from its second)
             const int cg = n_tile * NT + tid;
 #pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                GroupStat* st = k ? a.st_out : a.st_raw;
+            for (int k = 0; k < KINDS / 2; ++k) {
+                GroupStat* st = k == 0 ? a.st_raw : (k == 1 ? a.st_out : a.st_pool);
                 if (!st) continue;
-                const int gs = (k ? a.st_out_C : a.st_raw_C) / GN_GROUPS, co = k ? a.st_out_co : a.st_raw_co;
+                const int gs = (k == 0 ? a.st_raw_C : (k == 1 ? a.st_out_C : a.st_pool_C)) / GN_GROUPS;
+                const int co = k == 0 ? a.st_raw_co : (k == 1 ? a.st_out_co : a.st_pool_co);
                 float t1 = 0.f, t2 = 0.f;
 #pragma unroll
                 for (int g = 0; g < NSEG; ++g) { t1 += red[g * RL + (2 * k) * NT + tid]; t2 += red[g * RL + (2 * k + 1) * NT + tid]; }
@@ -646,11 +709,14 @@ __global__ __launch_bounds__(MWT, 1) void conv_mw_kernel(ConvArgs a) {
                 if (tid % gs == (gs > 1 ? 1 : 0)) stat_add(&o->sq, act_hi_cells(a.B), s2);
             }
         }
+    };
+    if (want_stats) {   // uniform over the grid
+        reduce_stats(std::integral_constant<int, POOL ? 6 : 4>{});
     }
     MWSTAMP(5);
 }
 
-template <typename T, int TAPS, int TH, int NT, int TPS, int NSLOT, bool GN, bool SC>
+template <typename T, int TAPS, int TH, int NT, int TPS, int NSLOT, bool GN, bool SC, bool POOL = false>
 int launch_mw_t(chore_handle* h, const ConvArgs& a, hipStream_t s) {
     using G = MGeo<TAPS, TH, NT, TPS, NSLOT, IS_X3<T>, std::is_same<T, bf16_t>::value ? 1 : 2>;
     size_t smem = G::smem_bytes(a.in.C);
@@ -668,7 +734,7 @@ int launch_mw_t(chore_handle* h, const ConvArgs& a, hipStream_t s) {
     if (smem < lds_min) smem = lds_min;
     const int tiles = ((a.W + PTW - 1) / PTW) * ((a.H + TH - 1) / TH);
     dim3 grid(tiles * (a.Cout / NT) * a.B);
-    return CHORE_LAUNCH(h, s, (conv_mw_kernel<T, TAPS, TH, NT, TPS, NSLOT, GN, SC>), grid, dim3(MWT), chore_lds(smem, lds_cu), a);
+    return CHORE_LAUNCH(h, s, (conv_mw_kernel<T, TAPS, TH, NT, TPS, NSLOT, GN, SC, POOL>), grid, dim3(MWT), chore_lds(smem, lds_cu), a);
 }
 
 }  // namespace
@@ -729,13 +795,22 @@ bool conv_mw_covers(int dtype, int taps, const PcPlan& p, const ConvArgs& a) {
     return conv_mw_has(p);
 }
 
+bool conv_mw_pool_covers(int dtype, int taps, int Cin, int Cout, int H, int W) {
+    // (conv_mw_plan has a tiling for every such layer: conv_pc_plan's fall-through is 8 or 4 rows x 32 channels)
+    return conv_mw_on(dtype, taps) && Cin % 32 == 0 && Cin <= 256 && Cout % 32 == 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0;
+}
+
 int launch_conv_mw(chore_handle* h, int dtype, int taps, const PcPlan& p, const ConvArgs& a, hipStream_t s) {
+    if (a.pool.p && ((a.H | a.W) & 1)) CHORE_FAIL(h, CHORE_EINVAL, "conv_mw: a pooled output needs even H and W (%d x %d)", a.H, a.W);
+    if (!a.pool.p && !a.out.p) CHORE_FAIL(h, CHORE_EINVAL, "conv_mw: no output");
+    if (a.pool.p && a.in_amax) CHORE_FAIL(h, CHORE_EINVAL, "conv_mw: no pooled output on the data-gradient kernels");
     chore_note_conv(h, CONV_FAM_MW, p.th, p.nt, p.tps, p.nslot, conv_note_flags(a), a.in.C);
     const int key = (p.th * 1000 + p.nt) * 100 + p.tps * 10 + p.nslot;
 #define MW_CASE(TH, NT, TPS, NSLOT) \
     case (TH * 1000 + NT) * 100 + TPS * 10 + NSLOT:                                              \
         return a.in_amax ? launch_mw_t<x3_t, 9, TH, NT, TPS, NSLOT, false, true>(h, a, s)         \
-                         : launch_mw_t<x3_t, 9, TH, NT, TPS, NSLOT, true, false>(h, a, s)
+               : (a.pool.p ? launch_mw_t<x3_t, 9, TH, NT, TPS, NSLOT, true, false, true>(h, a, s) \
+                           : launch_mw_t<x3_t, 9, TH, NT, TPS, NSLOT, true, false>(h, a, s))
     switch (key) {
         MW_CASE(8, 128, 1, 3);
         MW_CASE(4, 128, 1, 3);

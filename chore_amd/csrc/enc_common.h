@@ -185,6 +185,12 @@ struct ConvArgs {
     // the tensor `raw` / `out` belong to; *_C = channels of that tensor (group size = C/32), *_co = offset of this slice
     GroupStat* st_raw = nullptr; int st_raw_C = 0, st_raw_co = 0;
     GroupStat* st_out = nullptr; int st_out_C = 0, st_out_co = 0;
+    // optional pooled output (B, H/2, W/2), a channel slice like `out`: the 2x2 average of the values `out` stores, formed in the
+    // epilogue as (((a + b) + c) + d) * 0.25f with a, b, c, d = (y,x), (y,x+1), (y+1,x), (y+1,x+1) -- bit for bit what
+    // launch_avgpool2 makes of `out` -- and its statistics.  H and W even; out.p may be null then (only the pooled tensor is wanted).
+    // Only launches for which conv_pool_covers() holds take it; launch_conv refuses it elsewhere
+    View pool;
+    GroupStat* st_pool = nullptr; int st_pool_C = 0, st_pool_co = 0;
     // fp16 x 3 only: range of the INPUT when it is a gradient (the data-gradient convolutions of training, whose operand has no
     // GroupNorm in front and any magnitude): AMAX_CELLS partial maxima of |x| as float bits (absmax_* in enc_common.h).  The
     // kernel multiplies the operand by the power of two that brings the maximum to 2^13 .. 2^14 before the hi / lo split (fp16
@@ -249,7 +255,7 @@ template <> struct Vec4<h16_t> {
 // the flag word of chore_handle::last_conv for a launch with these arguments
 inline int conv_note_flags(const ConvArgs& a, bool small_grid = false) {
     return (a.in_amax ? CONV_FLAG_SCALED : 0) | (a.in_st ? CONV_FLAG_GN : 0) | (small_grid ? CONV_FLAG_SMALL_GRID : 0) |
-           (a.res.p ? CONV_FLAG_RES : 0);
+           (a.res.p ? CONV_FLAG_RES : 0) | (a.pool.p ? CONV_FLAG_POOL : 0);
 }
 
 struct ConvPlan { int nt, th, ntiles, tps, small_cin; };   // N tile, tile height, tiles per image, taps per K-step (tps 0: conv_small_kernel)
@@ -271,6 +277,11 @@ bool conv_mw_on(int dtype, int taps);   // by mode: fp16 x 3, 3x3, not switched 
 PcPlan conv_mw_plan(int dtype, int taps, int B, int H, int W, int Cin, int Cout, int fill);   // conv_pc_plan's tiling, or one only this kernel has
 bool conv_mw_has(const PcPlan& p);      // an instantiation for this tiling exists
 bool conv_mw_covers(int dtype, int taps, const PcPlan& p, const ConvArgs& a);
+// a launch of this layer can carry a pooled output (ConvArgs::pool): by mode, taps, channels and even H and W -- never by the batch
+// size (one image alone and the same image inside a batch must take the same path).  Every tiling conv_mw_plan yields pools
+bool conv_mw_pool_covers(int dtype, int taps, int Cin, int Cout, int H, int W);
+// the same question for whichever kernel launch_conv picks (conv_mw_kernel only; the 1x1 layers keep the pooling pass: DESIGN section 4)
+bool conv_pool_covers(int dtype, int taps, int Cin, int Cout, int H, int W);
 int launch_conv_mw(chore_handle* h, int dtype, int taps, const PcPlan& p, const ConvArgs& a, hipStream_t s);
 // 1x1 layers (fp16 x 3, fp16, bf16) with register-resident weights (conv_rw.hip): persistent workgroups over runs of pixel blocks
 bool conv_rw_covers(int dtype, int taps, int Cin, int Cout, bool scaled_input);   // by shape (scaled_input: ConvArgs::in_amax set)
@@ -302,8 +313,9 @@ int launch_pack_stem(chore_handle* h, int Cin, const float* w /*(64,Cin,7,7)*/, 
 size_t stem_x3_bytes();
 bool stem_x3_on(int Cin);
 int launch_pack_stem_x3(chore_handle* h, int Cin, const float* w, void* dst, hipStream_t s);
+// st (or null): zeroed accumulators that receive the GroupNorm(32, 64) statistics of `out` from the same launch
 int launch_stem_x3(chore_handle* h, const float* images, int B, int Cin, int H, int W, const void* wfr, const float* bias, float* out,
-                   hipStream_t s);
+                   hipStream_t s, GroupStat* st = nullptr);
 // statistics of a tensor no convolution produced (pooling / upsampling / stem outputs): one pass, atomics
 int launch_gn_stats(chore_handle* h, int dtype, const View& x, int B, int HW, GroupStat* st, hipStream_t s);
 // train_bwd.hip: the layer backward pieces with channel-strided gradients (what a ConvBlock's concat hands its convs)

@@ -173,7 +173,7 @@ constexpr int SX_TW = 32, SX_PW = 2 * SX_TW + 5, SX_PS2 = 72;      // patch colu
 template <int CIN>
 __global__ __launch_bounds__(256) void stem_x3_kernel(const float* __restrict__ img, int B, int H, int W,
                                                       const u32x4* __restrict__ wfr, const float* __restrict__ bias,
-                                                      float* __restrict__ out) {
+                                                      float* __restrict__ out, GroupStat* __restrict__ st) {
     f16_saturate_mode();
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* patch = sm;                                   // [CIN][37][SX_PS2]
@@ -265,6 +265,11 @@ __global__ __launch_bounds__(256) void stem_x3_kernel(const float* __restrict__ 
         if (ks + SX_PF < SX_KS) load_frag(f, ks + SX_PF);
     }
     const float inv = 1.0f / (float)(1 << X3_WSHIFT);
+    // statistics of what is stored (st != null, uniform): GroupNorm(32, 64) = pairs of channels; a lane's quad of channels
+    // rb * 32 + 8 g + 4 half + 0 .. 3 is two groups.  ps / pq[(rb * 4 + g) * 2 + pair]: this lane's four pixels, in a fixed order
+    float ps[16], pq[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) ps[i] = pq[i] = 0.f;
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb) {
         const int oy = ty0 + 4 * wv + cb, ox = tx0 + col;
@@ -276,8 +281,38 @@ __global__ __launch_bounds__(256) void stem_x3_kernel(const float* __restrict__ 
                 for (int g = 0; g < 4; ++g) {
                     const f32x4 v = {acc[rb][cb][4 * g] * inv, acc[rb][cb][4 * g + 1] * inv, acc[rb][cb][4 * g + 2] * inv, acc[rb][cb][4 * g + 3] * inv};
                     *(f32x4*)(o + rb * 32 + 8 * g + 4 * half) = v;
+                    if (st) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const int i = (rb * 4 + g) * 2 + (e >> 1);
+                            ps[i] += v[e];
+                            pq[i] = fmaf(v[e], v[e], pq[i]);
+                        }
+                    }
                 }
         }
+    }
+    if (!st) return;   // uniform over the grid
+    // the 32 pixels of a half wave by a fixed tree, the four waves in a fixed order, one exact add per (group, kind) and workgroup
+    __shared__ float sred[4][2][32];
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+#pragma unroll
+        for (int o = 1; o < 32; o <<= 1) { ps[i] += __shfl_xor(ps[i], o, 64); pq[i] += __shfl_xor(pq[i], o, 64); }
+    if (col == 0) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { sred[wv][half][i] = ps[i]; sred[wv][half][16 + i] = pq[i]; }
+    }
+    __syncthreads();
+    if (tid < 64) {
+        const int kind = tid >> 5, gi = tid & 31;               // group gi = channels 2 gi, 2 gi + 1
+        const int rb = gi >> 4, ch = 2 * gi - 32 * rb, g = ch >> 3, hf = (ch >> 2) & 1, pair = (ch >> 1) & 1;
+        const int i = kind * 16 + (rb * 4 + g) * 2 + pair;
+        float t = 0.f;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) t += sred[w][hf][i];
+        GroupStat* o = st + (size_t)b * GN_GROUPS + gi;
+        stat_add(kind ? &o->sq : &o->sum, act_hi_cells(B), t);
     }
 }
 
@@ -295,13 +330,13 @@ bool stem_x3_on(int Cin) {
     return !off && (Cin == 5 || Cin == 4 || Cin == 3);
 }
 int launch_stem_x3(chore_handle* h, const float* images, int B, int Cin, int H, int W, const void* wfr, const float* bias, float* out,
-                   hipStream_t s) {
+                   hipStream_t s, GroupStat* st) {
     const int OH = H / 2, OW = W / 2;
     dim3 grid((OW + SX_TW - 1) / SX_TW, (OH + STEM_T - 1) / STEM_T, B);
     const size_t smem = (size_t)Cin * STEM_P * SX_PS2 * sizeof(float);       // 53 KB for five channels
-    if (Cin == 5) return CHORE_LAUNCH(h, s, stem_x3_kernel<5>, grid, dim3(256), smem, images, B, H, W, (const u32x4*)wfr, bias, out);
-    if (Cin == 4) return CHORE_LAUNCH(h, s, stem_x3_kernel<4>, grid, dim3(256), smem, images, B, H, W, (const u32x4*)wfr, bias, out);
-    if (Cin == 3) return CHORE_LAUNCH(h, s, stem_x3_kernel<3>, grid, dim3(256), smem, images, B, H, W, (const u32x4*)wfr, bias, out);
+    if (Cin == 5) return CHORE_LAUNCH(h, s, stem_x3_kernel<5>, grid, dim3(256), smem, images, B, H, W, (const u32x4*)wfr, bias, out, st);
+    if (Cin == 4) return CHORE_LAUNCH(h, s, stem_x3_kernel<4>, grid, dim3(256), smem, images, B, H, W, (const u32x4*)wfr, bias, out, st);
+    if (Cin == 3) return CHORE_LAUNCH(h, s, stem_x3_kernel<3>, grid, dim3(256), smem, images, B, H, W, (const u32x4*)wfr, bias, out, st);
     CHORE_FAIL(h, CHORE_EINVAL, "stem (fp16 x 3): Cin = %d not instantiated", Cin);
 }
 

@@ -262,6 +262,11 @@ struct Builder {
     double cur_flops = 0.0, cur_bytes = 0.0;
     double es() const { return (double)esize(dtype); }
 
+    // The 2x2 average pooling of a ConvBlock's output rides in the epilogues of the block's three convolutions where every one of
+    // them can carry it (conv_pool_covers), and the output statistics nobody reads are not computed.  CHORE_ENC_NO_POOL_FOLD=1: every
+    // pooling pass and every ConvBlock statistic as before (A/B; the stem's statistics have CHORE_ENC_NO_STEM_STATS_FOLD)
+    bool pool_fold = true;
+    bool stem_stats_fold = true;   // CHORE_ENC_NO_STEM_STATS_FOLD=1: off
     bool no_merge = false;   // CHORE_ENC_NO_MERGE: keep l / bl / al separate in eval too (A/B and bit-comparison with training mode)
     explicit Builder(Program& p) : P(p), B(p.B), dtype(p.dtype) {
         concurrent = getenv("CHORE_ENC_SERIAL") == nullptr;
@@ -270,6 +275,8 @@ struct Builder {
         // others to new queues (~10 us per queue change): 5.43 against 5.53 ms per step.  CHORE_ENC_CHILD_FIRST=1: the old order.
         main_first = getenv("CHORE_ENC_CHILD_FIRST") == nullptr;
         no_merge = getenv("CHORE_ENC_NO_MERGE") != nullptr;
+        pool_fold = getenv("CHORE_ENC_NO_POOL_FOLD") == nullptr;
+        stem_stats_fold = getenv("CHORE_ENC_NO_STEM_STATS_FOLD") == nullptr;
     }
 
     Buf alloc(int H, int W, int C) {
@@ -365,6 +372,8 @@ struct Builder {
         bool has_res2 = false; Buf res2; int res2_co = 0;
         int taps = 9, cout = 0;
         bool stat_raw = false, stat_out = false;   // accumulate GroupNorm statistics of raw / out
+        bool no_out = false;                       // `out` is not written (only the pooled output is wanted; res may still read the buffer)
+        bool has_pool = false; Buf pool; int pool_co = 0;   // the 2x2 average of `out` and its statistics, from the epilogue
     };
     void conv(const ConvSpec& c) {
         const WEntry we = w(c.wname + ".weight");
@@ -380,7 +389,7 @@ struct Builder {
             const double px = (double)B * c.in.H * c.in.W;
             cur_class = conv_class_of(dtype, c.taps, B, c.in.H, c.in.W, c.in_C, c.cout);
             cur_flops = 2.0 * c.taps * c.in_C * c.cout * px;
-            cur_bytes = px * es() * (c.in_C + c.cout * (1 + (c.has_raw ? 1 : 0) + (c.has_res ? 1 : 0) + (c.has_res2 ? 1 : 0)));
+            cur_bytes = px * es() * (c.in_C + c.cout * ((c.no_out ? 0.0 : 1.0) + (c.has_pool ? 0.25 : 0.0) + (c.has_raw ? 1 : 0) + (c.has_res ? 1 : 0) + (c.has_res2 ? 1 : 0)));
         }
         const int Bn = B;
         push([=](RunCtx& r) {
@@ -395,7 +404,11 @@ struct Builder {
             }
             a.wpk = r.arena + we.off;
             a.bias = cs.bias ? (const float*)(r.arena + be.off) : nullptr;
-            a.out = view(r, cs.out, cs.out_co, cs.cout);
+            if (!cs.no_out) a.out = view(r, cs.out, cs.out_co, cs.cout);
+            if (cs.has_pool) {
+                a.pool = view(r, cs.pool, cs.pool_co, cs.cout);
+                a.st_pool = (GroupStat*)(r.stats + cs.pool.st_off); a.st_pool_C = cs.pool.C; a.st_pool_co = cs.pool_co;
+            }
             if (cs.has_raw) a.raw = view(r, cs.raw, cs.raw_co, cs.cout);
             if (cs.has_res) a.res = view(r, cs.res, cs.res_co, cs.cout);
             if (cs.has_res2) a.res2 = view(r, cs.res2, cs.res2_co, cs.cout);
@@ -410,13 +423,23 @@ struct Builder {
         });
     }
 
-    // ConvBlock (net_util.py:374-396): y = cat(o1,o2,o3) + residual; x must carry statistics
-    Buf conv_block(Buf& x, const std::string& n, int cin, int cout) {
+    // ConvBlock (net_util.py:374-396): y = cat(o1,o2,o3) + residual; x must carry statistics.
+    // out_unread: no GroupNorm reads the output as it leaves this block (upadd recomputes the statistics of what it modifies, conv_last
+    //   has no GroupNorm) -- the output carries no statistics then and must not be handed to ensure_stats.
+    // pool: a (H/2, W/2, cout) buffer for avgpool2(y).  Where the three convolutions can carry it, it is written by their epilogues and
+    //   comes back with st_valid set; otherwise it is left untouched and the caller runs the pooling pass.
+    // keep_out = false (with pool): y itself has no other reader and is not written when the pooling folds
+    Buf conv_block(Buf& x, const std::string& n, int cin, int cout, bool out_unread = false, Buf* pool = nullptr, bool keep_out = true) {
         const int H = x.H, W = x.W;
         ensure_stats(x);
         Buf out = alloc(H, W, cout);
         Buf o1 = alloc(H, W, cout / 2), o2 = alloc(H, W, cout / 4);
-        new_stats(out);
+        const bool fold = pool_fold && pool && conv_pool_covers(dtype, 9, cin, cout / 2, H, W) &&
+                          conv_pool_covers(dtype, 9, cout / 2, cout / 4, H, W) && conv_pool_covers(dtype, 9, cout / 4, cout / 4, H, W);
+        const bool st_out = !(pool_fold && (out_unread || (fold && !keep_out)));
+        const bool wr_out = !(fold && !keep_out);
+        if (fold) new_stats(*pool);
+        if (st_out) new_stats(out);
         new_stats(o1);
         new_stats(o2);
         Buf res = x;
@@ -430,17 +453,20 @@ struct Builder {
         ConvSpec c1;
         c1.in = x; c1.in_C = cin; c1.gn = n + ".bn1"; c1.wname = n + ".conv1";
         c1.out = out; c1.out_co = 0; c1.has_raw = true; c1.raw = o1; c1.has_res = true; c1.res = res; c1.res_co = 0;
-        c1.cout = cout / 2; c1.stat_raw = true; c1.stat_out = true;
+        c1.cout = cout / 2; c1.stat_raw = true; c1.stat_out = st_out; c1.no_out = !wr_out;
+        if (fold) { c1.has_pool = true; c1.pool = *pool; c1.pool_co = 0; }
         conv(c1);
         ConvSpec c2;
         c2.in = o1; c2.in_C = cout / 2; c2.gn = n + ".bn2"; c2.wname = n + ".conv2";
         c2.out = out; c2.out_co = cout / 2; c2.has_raw = true; c2.raw = o2; c2.has_res = true; c2.res = res;
-        c2.res_co = cout / 2; c2.cout = cout / 4; c2.stat_raw = true; c2.stat_out = true;
+        c2.res_co = cout / 2; c2.cout = cout / 4; c2.stat_raw = true; c2.stat_out = st_out; c2.no_out = !wr_out;
+        if (fold) { c2.has_pool = true; c2.pool = *pool; c2.pool_co = cout / 2; }
         conv(c2);
         ConvSpec c3;
         c3.in = o2; c3.in_C = cout / 4; c3.gn = n + ".bn3"; c3.wname = n + ".conv3";
         c3.out = out; c3.out_co = 3 * cout / 4; c3.has_res = true; c3.res = res; c3.res_co = 3 * cout / 4;
-        c3.cout = cout / 4; c3.stat_out = true;
+        c3.cout = cout / 4; c3.stat_out = st_out; c3.no_out = !wr_out;
+        if (fold) { c3.has_pool = true; c3.pool = *pool; c3.pool_co = 3 * cout / 4; }
         conv(c3);
         release(o1);
         release(o2);
@@ -475,7 +501,8 @@ struct Builder {
 
     // HourGlass._forward (HGFilters.py:26-50).  The upper branch (b1 at full resolution) is independent
     // of the whole lower branch: it runs on its own stream.
-    Buf hourglass(Buf& x, const std::string& n, int level) {
+    // pooled_x: a buffer for avgpool2(x) the caller allocated on the current stream; st_valid: x's producer already filled it
+    Buf hourglass(Buf& x, const std::string& n, int level, Buf* pooled_x = nullptr) {
         const std::string l = std::to_string(level);
         const int child = P.cfg.num_hourglass - level + 1;   // 1 for the outermost level
         ensure_stats(x);   // on the current stream, before the fork: both branches read them
@@ -484,19 +511,27 @@ struct Builder {
         Buf up1;
         if (!(concurrent && main_first)) {
             if (concurrent) cur = child;
-            up1 = conv_block(x, n + ".b1_" + l, 256, 256);
+            up1 = conv_block(x, n + ".b1_" + l, 256, 256, true);
             cur = parent;
         }
-        Buf pooled = pool2(x);
-        Buf low1 = conv_block(pooled, n + ".b2_" + l, 256, 256);
-        release(pooled);
-        Buf low2 = (level > 1) ? hourglass(low1, n, level - 1) : conv_block(low1, n + ".b2_plus_" + l, 256, 256);
+        Buf pooled = !pooled_x ? pool2(x) : (pooled_x->st_valid ? *pooled_x : pool2(x, pooled_x));
+        Buf low1, low2;
+        if (level > 1) {     // low1 is pooled by the next level: its producers carry the pooled output
+            Buf pooled1 = alloc(pooled.H / 2, pooled.W / 2, 256);
+            low1 = conv_block(pooled, n + ".b2_" + l, 256, 256, false, &pooled1);
+            release(pooled);
+            low2 = hourglass(low1, n, level - 1, &pooled1);
+        } else {
+            low1 = conv_block(pooled, n + ".b2_" + l, 256, 256);
+            release(pooled);
+            low2 = conv_block(low1, n + ".b2_plus_" + l, 256, 256);
+        }
         release(low1);
-        Buf low3 = conv_block(low2, n + ".b3_" + l, 256, 256);
+        Buf low3 = conv_block(low2, n + ".b3_" + l, 256, 256, true);
         release(low2);
         if (concurrent && main_first) {
             cur = child;
-            up1 = conv_block(x, n + ".b1_" + l, 256, 256);
+            up1 = conv_block(x, n + ".b1_" + l, 256, 256, true);
             cur = parent;
         }
         join(child);
@@ -521,6 +556,12 @@ struct Builder {
         {
             const WEntry we = w(p + "conv1.weight"), be = w(p + "conv1.bias");
             const int Cin = cfg.in_channels, H = P.H, W = P.W;
+            // the matrix-core stem accumulates the statistics of the map it stores (bn1 needs them): no gn_stats pass over c1.
+            // CHORE_ENC_NO_STEM_STATS_FOLD=1: the pass as before (A/B).  A switch of its own: the stem's partial sums are not the
+            // pass's, so tmpx moves in its last bits with it, while CHORE_ENC_NO_POOL_FOLD leaves tmpx and normx bit for bit alone
+            const bool stem_stats = stem_stats_fold && dtype == CHORE_F16X3 && stem_x3_on(Cin);
+            if (stem_stats) new_stats(c1);
+            const Buf c1s = c1;
             cur_label = "stem";
             cur_class = K_STEM; cur_flops = 2.0 * 49 * Cin * 64 * (double)B * (H / 2) * (W / 2);
             cur_bytes = (double)B * H * W * Cin * 4 + (double)B * (H / 2) * (W / 2) * 64 * es();
@@ -528,7 +569,8 @@ struct Builder {
                 if (r.rc) return;
                 if (r.dtype == CHORE_F16X3 && stem_x3_on(Cin))
                     r.rc = launch_stem_x3(r.h, r.images, Bn, Cin, H, W, r.arena + we.off + (size_t)Cin * 49 * 64 * 4,
-                                          (const float*)(r.arena + be.off), (float*)ptr(r, c1), r.s);
+                                          (const float*)(r.arena + be.off), (float*)ptr(r, c1), r.s,
+                                          stem_stats ? (GroupStat*)(r.stats + c1s.st_off) : nullptr);
                 else
                     r.rc = launch_stem(r.h, sdt(r.dtype), r.images, Bn, Cin, H, W, (const float*)(r.arena + we.off),
                                        (const float*)(r.arena + be.off), ptr(r, c1), r.s);
@@ -553,18 +595,23 @@ struct Builder {
             });
         }
         release(c1);
-        Buf b2 = conv_block(tmpx, p + "conv2", 64, 128);
+        // b2 is read by its pooling alone: where the pooling folds, only normx is written (the block's buffer then holds just the
+        // 1x1 downsample the three convolutions read as their residual)
         Buf normx = P.want_normx ? external(101, H4, W4, 128) : alloc(H4, W4, 128);
-        normx = pool2(b2, &normx);
+        Buf b2 = conv_block(tmpx, p + "conv2", 64, 128, false, &normx, false);
+        if (!normx.st_valid) normx = pool2(b2, &normx);
         release(b2);
         Buf x3 = conv_block(normx, p + "conv3", 128, 128);
         release(normx);
-        Buf previous = conv_block(x3, p + "conv4", 128, 256);
+        // the first stack's hourglass pools `previous` first thing: conv4 carries the pooled output.  (The later stacks' `previous` comes
+        // from the merged 1x1 layer on conv_rw_kernel, which keeps the pooling pass: measured no gain)
+        Buf pooled0 = alloc(H4 / 2, W4 / 2, 256);
+        Buf previous = conv_block(x3, p + "conv4", 128, 256, false, &pooled0);
         release(x3);
         for (int i = 0; i < cfg.num_stack; ++i) {
             const std::string s = std::to_string(i);
-            Buf hg = hourglass(previous, p + "m" + s, cfg.num_hourglass);
-            Buf t1 = conv_block(hg, p + "top_m_" + s, 256, 256);
+            Buf hg = hourglass(previous, p + "m" + s, cfg.num_hourglass, i == 0 ? &pooled0 : nullptr);
+            Buf t1 = conv_block(hg, p + "top_m_" + s, 256, 256, true);
             release(hg);
             Buf t2 = alloc(H4, W4, 256);
             new_stats(t2);

@@ -73,6 +73,45 @@ int chore_conv2d_fwd(chore_handle* h, int dtype, int taps, const void* x, int B,
     return launch_conv(h, dtype, taps, a, s);
 }
 
+// chore_conv2d_fwd with a residual and a pooled output: y = conv(a) + bias + res (res (B,H,W,Cout) or NULL; may be y),
+// y_pool (B,H/2,W/2,Cout) = avgpool2(y) bit for bit, pool_stats (or NULL): ZEROED accumulators that receive the statistics of y_pool.
+// Where the launch can carry the pooled output (conv_pool_covers: the 3x3 layers of the fp16 x 3 mode, even H and W) it leaves from the
+// convolution's epilogue and y may be NULL (only y_pool is written); elsewhere the convolution is followed by the pooling pass, which
+// needs y.  H and W even
+int chore_conv2d_pool_fwd(chore_handle* h, int dtype, int taps, const void* x, int B, int H, int W, int Cin,
+                          const void* stats, const float* gamma, const float* beta, const float* w, const float* bias,
+                          int Cout, const void* res, void* y, void* out_stats, void* y_pool, void* pool_stats, void* workspace,
+                          chore_stream_t stream) {
+    CHORE_ENTER(h);
+    if (!x || !w || !y_pool || !workspace) CHORE_FAIL(h, CHORE_EINVAL, "chore_conv2d_pool_fwd: null argument");
+    if (stats && (!gamma || !beta)) CHORE_FAIL(h, CHORE_EINVAL, "chore_conv2d_pool_fwd: GroupNorm needs gamma and beta");
+    if (B <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) CHORE_FAIL(h, CHORE_EINVAL, "chore_conv2d_pool_fwd: H and W must be even");
+    hipStream_t s = (hipStream_t)stream;
+    const bool fold = stats && conv_pool_covers(dtype, taps, Cin, Cout, H, W);
+    if (!fold && !y) CHORE_FAIL(h, CHORE_EINVAL, "chore_conv2d_pool_fwd: this layer pools in a pass of its own, which needs y");
+    int rc = launch_pack_conv(h, dtype, taps, Cin, Cout, w, workspace, s, 0);
+    if (rc) return rc;
+    ConvArgs a{};
+    a.in.p = const_cast<void*>(x); a.in.cs = Cin; a.in.co = 0; a.in.C = Cin;
+    a.in_st = (const GroupStat*)stats; a.gamma = gamma; a.beta = beta;
+    a.wpk = workspace; a.bias = bias;
+    a.out.p = y; a.out.cs = Cout; a.out.co = 0; a.out.C = Cout;
+    if (res) { a.res.p = const_cast<void*>(res); a.res.cs = Cout; a.res.co = 0; a.res.C = Cout; }
+    a.B = B; a.H = H; a.W = W; a.Cout = Cout;
+    if (out_stats && y) { a.st_out = (GroupStat*)out_stats; a.st_out_C = Cout; a.st_out_co = 0; }
+    View vp; vp.p = y_pool; vp.cs = Cout; vp.co = 0; vp.C = Cout;
+    if (fold) {
+        a.pool = vp;
+        if (pool_stats) { a.st_pool = (GroupStat*)pool_stats; a.st_pool_C = Cout; a.st_pool_co = 0; }
+        return launch_conv(h, dtype, taps, a, s);
+    }
+    rc = launch_conv(h, dtype, taps, a, s);
+    if (rc) return rc;
+    const int edt = elem_dtype(dtype);
+    if (edt != CHORE_F32 && edt != CHORE_BF16) CHORE_FAIL(h, CHORE_EINVAL, "chore_conv2d_pool_fwd: dtype");
+    return launch_avgpool2(h, edt, a.out, vp, B, H, W, (GroupStat*)pool_stats, s);
+}
+
 // dx (B,H,W,Cin) = gradient of the convolution's INPUT (the tensor the conv saw, after any GroupNorm+ReLU):
 // the same kernel on the transposed, spatially flipped weights
 // dy_amax: the range of dy (chore_absmax_f32), required with dtype CHORE_F16X3, ignored otherwise
@@ -108,6 +147,21 @@ int chore_stem_fwd(chore_handle* h, int dtype, const float* images, int B, int C
     int rc = launch_pack_stem(h, Cin, w, (float*)workspace, s);
     if (rc) return rc;
     return launch_stem(h, dtype, images, B, Cin, H, W, (const float*)workspace, bias, y, s);
+}
+
+// the stem of the fp16 x 3 mode (stem_x3_kernel: the matrix cores, hi / lo split operands; Cin 3, 4 or 5), fp32 y, with the statistics
+// of y from the same launch.  out_stats (or NULL): ZEROED chore_gn_stats_bytes(B) accumulators.  workspace: chore_stem_x3_workspace_bytes(Cin)
+size_t chore_stem_x3_workspace_bytes(int Cin) { return Cin > 0 ? stem_x3_bytes() : 0; }
+
+int chore_stem_x3_fwd(chore_handle* h, const float* images, int B, int Cin, int H, int W, const float* w, const float* bias, void* y,
+                      void* out_stats, void* workspace, chore_stream_t stream) {
+    CHORE_ENTER(h);
+    if (!images || !w || !bias || !y || !workspace) CHORE_FAIL(h, CHORE_EINVAL, "chore_stem_x3_fwd: null argument");
+    if (B <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) CHORE_FAIL(h, CHORE_EINVAL, "chore_stem_x3_fwd: bad shape");
+    if (Cin != 3 && Cin != 4 && Cin != 5) CHORE_FAIL(h, CHORE_EINVAL, "chore_stem_x3_fwd: Cin = %d not instantiated", Cin);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = launch_pack_stem_x3(h, Cin, w, workspace, s)) return rc;
+    return launch_stem_x3(h, images, B, Cin, H, W, workspace, bias, (float*)y, s, (GroupStat*)out_stats);
 }
 
 // y (B,H/2,W/2,C) = 2x2 average pooling of x (B,H,W,C), C in {64,128,256}; dx = its transpose applied to dy

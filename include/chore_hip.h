@@ -527,6 +527,14 @@ int chore_gn_relu_fwd(chore_handle* h, int dtype, const void* x, const void* sta
 int chore_conv2d_fwd(chore_handle* h, int dtype, int taps, const void* x, int B, int H, int W, int Cin,
                      const void* stats, const float* gamma, const float* beta, const float* w, const float* bias,
                      int Cout, void* y, void* out_stats, void* workspace, chore_stream_t stream);
+/* chore_conv2d_fwd with a residual and a pooled output: y = conv(a) + bias + res (res (B,H,W,Cout) or NULL), y_pool (B,H/2,W/2,Cout) =
+ * the 2x2 average of y exactly as chore_avgpool2_fwd forms it, pool_stats (or NULL): ZEROED accumulators for the statistics of
+ * y_pool.  H and W even.  Where the convolution's epilogue can carry the pooled output (CHORE_F16X3, 3x3, GroupNorm fused) y may be
+ * NULL: only y_pool is written.  Elsewhere the pooling runs as a pass over y (y required; Cout 64, 128 or 256) */
+int chore_conv2d_pool_fwd(chore_handle* h, int dtype, int taps, const void* x, int B, int H, int W, int Cin,
+                          const void* stats, const float* gamma, const float* beta, const float* w, const float* bias,
+                          int Cout, const void* res, void* y, void* out_stats, void* y_pool, void* pool_stats, void* workspace,
+                          chore_stream_t stream);
 /* dx (B,H,W,Cin) = gradient w.r.t. the tensor the convolution saw (a).  dy_amax: chore_absmax_f32 of dy, required with
  * CHORE_F16X3 (NULL otherwise); the same for chore_conv2d_bwd_weight */
 int chore_conv2d_bwd_data(chore_handle* h, int dtype, int taps, const void* dy, int B, int H, int W, int Cout,
@@ -592,6 +600,11 @@ int chore_avgpool2_bwd(chore_handle* h, int dtype, const void* dy, void* dx, int
 size_t chore_stem_workspace_bytes(int Cin);
 int chore_stem_fwd(chore_handle* h, int dtype, const float* images, int B, int Cin, int H, int W, const float* w,
                    const float* bias, void* y, void* workspace, chore_stream_t stream);
+/* the stem of the CHORE_F16X3 mode (matrix cores, hi / lo split operands; Cin 3, 4 or 5): fp32 y (B,H/2,W/2,64) and, with out_stats
+ * != NULL (ZEROED accumulators), the GroupNorm statistics of y from the same launch */
+size_t chore_stem_x3_workspace_bytes(int Cin);
+int chore_stem_x3_fwd(chore_handle* h, const float* images, int B, int Cin, int H, int W, const float* w, const float* bias,
+                      void* y, void* out_stats, void* workspace, chore_stream_t stream);
 size_t chore_stem_wgrad_workspace_bytes(int B, int Cin, int H, int W);
 int chore_stem_bwd_weight(chore_handle* h, int dtype, const float* images, int B, int Cin, int H, int W, const void* dy,
                           float* dw, float* dbias, void* workspace, chore_stream_t stream);
@@ -728,7 +741,7 @@ int chore_debug_nan_counts(unsigned* out32);
  *   out[1] rows of a tile (conv_small_kernel: rows per workgroup; conv_rw_kernel: 0)   out[2] output channels per workgroup
  *   out[3] taps per K-step   out[4] K-steps of weights resident in LDS (0 where the kernel has no such ring)
  *   out[5] flags: 1 scaled-input variant (data gradient of CHORE_F16X3), 2 GroupNorm fused into the input, 4 small-grid variant
- *          of conv_lds_kernel, 8 residual added in the epilogue
+ *          of conv_lds_kernel, 8 residual added in the epilogue, 16 pooled output written by the epilogue
  *   out[6] input channels   out[7] convolution launches on the handle so far
  * Host stores only: no kernel and no result changes. */
 int chore_debug_last_conv(chore_handle* h, int* out, int n);
