@@ -729,9 +729,7 @@ int launch_mw_t(chore_handle* h, const ConvArgs& a, hipStream_t s) {
     // convolution: the encoder's maps were equal); 128 KB: 1 of 128; 160 KB: 0 of 128.  conv_pc_kernel never shared a CU either
     // (8 waves x 256 registers).  What exactly goes wrong when LDS-using workgroups of other kernels sit beside these four
     // 1-wave-per-SIMD MFMA waves is NOT understood; the cost of the exclusion is nil inside the kernel.
-    static const size_t lds_min_env = getenv("CHORE_CONV_MW_LDS_MIN") ? (size_t)atol(getenv("CHORE_CONV_MW_LDS_MIN")) : 0;   // experiments
-    const size_t lds_min = lds_min_env ? lds_min_env : lds_cu;
-    if (smem < lds_min) smem = lds_min;
+    smem = lds_cu;
     const int tiles = ((a.W + PTW - 1) / PTW) * ((a.H + TH - 1) / TH);
     dim3 grid(tiles * (a.Cout / NT) * a.B);
     return CHORE_LAUNCH(h, s, (conv_mw_kernel<T, TAPS, TH, NT, TPS, NSLOT, GN, SC, POOL>), grid, dim3(MWT), chore_lds(smem, lds_cu), a);
@@ -773,10 +771,8 @@ PcPlan conv_mw_plan(int dtype, int taps, int B, int H, int W, int Cin, int Cout,
         if (px8 * (Cout / 32) < 256 || !p.th || (p.th == 4 && p.nt == 32) || (p.th == 8 && p.nt == 32 && px8 * (Cout / 32) < 512)) {
             static const int cand[][4] = {{8, 128, 1, 3}, {4, 128, 1, 3}, {2, 128, 1, 3}, {8, 64, 3, 2}, {4, 64, 3, 2}, {2, 64, 1, 3},
                                           {8, 32, 3, 2}, {4, 32, 9, 2}};
-            static const char* skip = getenv("CHORE_CONV_MW_SKIP");      // experiments: "th*1000+nt[,...]" tilings left out
             for (const auto& c : cand) {
                 if (Cout % c[1] || H % c[0]) continue;
-                if (skip) { char key[16]; snprintf(key, sizeof key, "%d", c[0] * 1000 + c[1]); if (strstr(skip, key)) continue; }
                 const long wgs = (long)B * (H / c[0]) * (W / 32) * (Cout / c[1]);
                 if (wgs >= fill) { p.th = c[0]; p.nt = c[1]; p.tps = c[2]; p.nslot = c[3]; break; }
             }

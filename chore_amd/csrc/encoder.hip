@@ -246,7 +246,7 @@ struct Program {
     size_t stats_off = 0, stats_bytes = 0;
     int n_events = 0, n_streams = 1;
     size_t ws_bytes = 0;
-    std::vector<hipEvent_t> events;       // created on first run: [group][n_events]
+    std::vector<hipEvent_t> events;       // created on first run: [n_events]
 };
 
 struct Builder {
@@ -256,7 +256,6 @@ struct Builder {
     int B, dtype;
     int cur = 0;           // stream the next steps are issued on
     bool concurrent;
-    bool main_first = false;
     std::string cur_label = "?";
     int cur_class = 0;
     double cur_flops = 0.0, cur_bytes = 0.0;
@@ -270,10 +269,6 @@ struct Builder {
     bool no_merge = false;   // CHORE_ENC_NO_MERGE: keep l / bl / al separate in eval too (A/B and bit-comparison with training mode)
     explicit Builder(Program& p) : P(p), B(p.B), dtype(p.dtype) {
         concurrent = getenv("CHORE_ENC_SERIAL") == nullptr;
-        // Issue order after a fork: the LOWER branch (the longer chain, on the forking stream) before the upper branch (child
-        // stream).  Replayed as a hipGraph the runtime keeps a node's first-recorded successor on the node's queue and moves the
-        // others to new queues (~10 us per queue change): 5.43 against 5.53 ms per step.  CHORE_ENC_CHILD_FIRST=1: the old order.
-        main_first = getenv("CHORE_ENC_CHILD_FIRST") == nullptr;
         no_merge = getenv("CHORE_ENC_NO_MERGE") != nullptr;
         pool_fold = getenv("CHORE_ENC_NO_POOL_FOLD") == nullptr;
         stem_stats_fold = getenv("CHORE_ENC_NO_STEM_STATS_FOLD") == nullptr;
@@ -508,12 +503,6 @@ struct Builder {
         ensure_stats(x);   // on the current stream, before the fork: both branches read them
         const int parent = cur;
         fork(child);
-        Buf up1;
-        if (!(concurrent && main_first)) {
-            if (concurrent) cur = child;
-            up1 = conv_block(x, n + ".b1_" + l, 256, 256, true);
-            cur = parent;
-        }
         Buf pooled = !pooled_x ? pool2(x) : (pooled_x->st_valid ? *pooled_x : pool2(x, pooled_x));
         Buf low1, low2;
         if (level > 1) {     // low1 is pooled by the next level: its producers carry the pooled output
@@ -529,11 +518,12 @@ struct Builder {
         release(low1);
         Buf low3 = conv_block(low2, n + ".b3_" + l, 256, 256, true);
         release(low2);
-        if (concurrent && main_first) {
-            cur = child;
-            up1 = conv_block(x, n + ".b1_" + l, 256, 256, true);
-            cur = parent;
-        }
+        // Issue order after a fork: the LOWER branch (the longer chain, on the forking stream) before the upper branch (child
+        // stream).  Replayed as a hipGraph the runtime keeps a node's first-recorded successor on the node's queue and moves the
+        // others to new queues (~10 us per queue change): 5.43 against 5.53 ms per step for the upper branch first (removed, round 8).
+        if (concurrent) cur = child;
+        Buf up1 = conv_block(x, n + ".b1_" + l, 256, 256, true);
+        cur = parent;
         join(child);
         upadd(up1, low3);
         release(low3);
@@ -670,27 +660,11 @@ struct Builder {
     }
 };
 
-constexpr int MAX_GROUPS = 8;
 struct EncCache {
     std::vector<std::unique_ptr<Program>> progs;
     Profile prof;
-    hipStream_t aux[MAX_GROUPS][MAX_STREAMS] = {};   // [0][0] unused (caller's stream)
-    hipEvent_t fork_ev = nullptr, join_ev[MAX_GROUPS] = {};
+    hipStream_t aux[MAX_STREAMS] = {};   // [0] unused (caller's stream)
 };
-
-// CHORE_ENC_GROUPS=G encodes the batch as G independent groups of B / G images, each a chain of launches of its own on its
-// own streams.  The idea: a launch of specialised-wave workgroups (one per CU) lasts as long as ONE workgroup lives, whether
-// it has 256 workgroups or 64, so the chains of half batches could overlap.  Measured (B = 4, fp16x3): G = 1 5.6 ms, G = 2
-// 6.9 ms, G = 4 10.7 ms per step with only 2.6 ms of host time at G = 2 -- the device does not run the chains side by side
-// (six and more streams share the hardware queues).  Off by default; kept as a switch.  Round 5, with hipGraph replays: two
-// recordings of a HALF batch side by side take 2 x 2.72 ms for the four images, one recording of the whole batch 5.31 ms (same
-// box): splitting the batch does not pay under replay either.
-int enc_groups(int B) {
-    static const int want = getenv("CHORE_ENC_GROUPS") ? atoi(getenv("CHORE_ENC_GROUPS")) : 1;
-    int g = want < 1 ? 1 : (want > MAX_GROUPS ? MAX_GROUPS : want);
-    while (g > 1 && B % g) --g;
-    return g;
-}
 
 Program* get_program(chore_handle* h, const chore_encoder_cfg& cfg, int B, int H, int W, int dtype, int n_out,
                      bool want_normx) {
@@ -734,12 +708,8 @@ extern "C" {
 void chore_encoder_cache_free(chore_handle* h) {
     if (h && h->enc_cache) {
         EncCache* c = (EncCache*)h->enc_cache;
-        for (int g = 0; g < MAX_GROUPS; ++g)
-            for (int i = 0; i < MAX_STREAMS; ++i)
-                if (c->aux[g][i]) (void)hipStreamDestroy(c->aux[g][i]);
-        if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
-        for (hipEvent_t e : c->join_ev)
-            if (e) (void)hipEventDestroy(e);
+        for (int i = 0; i < MAX_STREAMS; ++i)
+            if (c->aux[i]) (void)hipStreamDestroy(c->aux[i]);
         for (auto& p : c->progs)
             for (hipEvent_t e : p->events) (void)hipEventDestroy(e);
         for (hipEvent_t e : c->prof.ev) (void)hipEventDestroy(e);
@@ -818,8 +788,7 @@ int chore_encoder_pack(chore_handle* h, const chore_encoder_cfg* cfg, const chor
 size_t chore_encoder_workspace_bytes(const chore_encoder_cfg* cfg, int B, int H, int W, int dtype) {
     if (!cfg || B <= 0 || H <= 0 || W <= 0 || H % 16 || W % 16) return 0;
     if (dtype != CHORE_F32 && dtype != CHORE_BF16 && dtype != CHORE_F16X3 && dtype != CHORE_F16) return 0;
-    const int G = enc_groups(B);
-    return (size_t)G * align_up(plan_workspace(*cfg, B / G, H, W, dtype), 256);
+    return align_up(plan_workspace(*cfg, B, H, W, dtype), 256);
 }
 
 int chore_encode_fwd(chore_handle* h, const chore_encoder_cfg* cfg, const float* images, int B, int H, int W,
@@ -835,111 +804,78 @@ int chore_encode_fwd(chore_handle* h, const chore_encoder_cfg* cfg, const float*
         CHORE_FAIL(h, CHORE_EINVAL, "chore_encode_fwd: bad n_stack_out");
     for (int i = 0; i < n_stack_out; ++i)
         if (!feat_out[i]) CHORE_FAIL(h, CHORE_EINVAL, "chore_encode_fwd: null feat_out[%d]", i);
-    const int G = enc_groups(B), Bg = B / G;
-    if (G > 1) {   // CHORE_ENC_GROUPS (an experiment switch, off by default): its fork / join of the groups' chains crashes this
-                   // runtime's hipStreamEndCapture (round 5) -- refuse a recording instead
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        CHORE_HIP_CHECK(h, hipStreamIsCapturing((hipStream_t)stream, &cs));
-        if (cs != hipStreamCaptureStatusNone)
-            CHORE_FAIL(h, CHORE_EINVAL, "chore_encode_fwd: CHORE_ENC_GROUPS=%d cannot be recorded into a hipGraph (eager launches only)", G);
-    }
-    Program* P = get_program(h, *cfg, Bg, H, W, dtype, n_stack_out, normx != nullptr);
-    const size_t ws_group = align_up(P->ws_bytes, 256);
-    if (workspace_bytes < (size_t)G * ws_group)
-        CHORE_FAIL(h, CHORE_ENOMEM, "chore_encode_fwd: workspace %zu < %zu bytes", workspace_bytes, (size_t)G * ws_group);
+    Program* P = get_program(h, *cfg, B, H, W, dtype, n_stack_out, normx != nullptr);
+    if (workspace_bytes < align_up(P->ws_bytes, 256))
+        CHORE_FAIL(h, CHORE_ENOMEM, "chore_encode_fwd: workspace %zu < %zu bytes", workspace_bytes, align_up(P->ws_bytes, 256));
     EncCache* cache = (EncCache*)h->enc_cache;
     static const bool debug_sync = getenv("CHORE_DEBUG_SYNC") != nullptr;
     Profile& prof = cache->prof;
     const bool serial = prof.on || debug_sync;   // attribution / debugging: everything on the caller's stream
-    hipStream_t streams[MAX_GROUPS][MAX_STREAMS];
-    for (int g = 0; g < G; ++g)
-        for (int i = 0; i < P->n_streams; ++i) {   // auxiliary streams / events are created once, not per call
-            if (g == 0 && i == 0) { streams[0][0] = (hipStream_t)stream; continue; }
-            if (!cache->aux[g][i]) CHORE_HIP_CHECK(h, hipStreamCreateWithFlags(&cache->aux[g][i], hipStreamNonBlocking));
-            streams[g][i] = cache->aux[g][i];
-        }
-    while ((int)P->events.size() < G * P->n_events) {
+    hipStream_t streams[MAX_STREAMS];
+    streams[0] = (hipStream_t)stream;
+    for (int i = 1; i < P->n_streams; ++i) {   // auxiliary streams / events are created once, not per call
+        if (!cache->aux[i]) CHORE_HIP_CHECK(h, hipStreamCreateWithFlags(&cache->aux[i], hipStreamNonBlocking));
+        streams[i] = cache->aux[i];
+    }
+    while ((int)P->events.size() < P->n_events) {
         hipEvent_t e;
         CHORE_HIP_CHECK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
         P->events.push_back(e);
     }
-    if (G > 1 && !serial) {   // the other groups' chains start where the caller's stream is now
-        if (!cache->fork_ev) CHORE_HIP_CHECK(h, hipEventCreateWithFlags(&cache->fork_ev, hipEventDisableTiming));
-        CHORE_HIP_CHECK(h, hipEventRecord(cache->fork_ev, (hipStream_t)stream));
-        for (int g = 1; g < G; ++g) CHORE_HIP_CHECK(h, hipStreamWaitEvent(streams[g][0], cache->fork_ev, 0));
-    }
     if (prof.on) {
-        const size_t need = 2 * P->steps.size() * G;
+        const size_t need = 2 * P->steps.size();
         while (prof.ev.size() < need) {
             hipEvent_t e;
             CHORE_HIP_CHECK(h, hipEventCreate(&e));
             prof.ev.push_back(e);
         }
     }
-    // element sizes of the caller's tensors (feature maps and tmpx / normx in the activation type)
-    const size_t es = esize(dtype);
-    const size_t img_stride = (size_t)cfg->in_channels * H * W;                          // floats per image
-    const size_t feat_stride = (size_t)(H / 4) * (W / 4) * cfg->hourglass_dim * es;      // bytes per image
-    const size_t tmpx_stride = (size_t)(H / 2) * (W / 2) * 64 * es, normx_stride = (size_t)(H / 4) * (W / 4) * 128 * es;
-    for (int g = 0; g < G; ++g) {
-        void* feats_g[16];
-        for (int i = 0; i < n_stack_out; ++i) feats_g[i] = (char*)feat_out[i] + (size_t)g * Bg * feat_stride;
-        RunCtx r;
-        r.h = h; r.dtype = dtype; r.s = streams[g][0]; r.arena = (const char*)arena;
-        char* ws = (char*)workspace + (size_t)g * ws_group;
-        for (int i = 0; i < MAX_STREAMS; ++i) r.pool_base[i] = ws + P->pool_off[i];
-        r.stats = ws + P->stats_off;
-        r.images = images + (size_t)g * Bg * img_stride;
-        r.feats = feats_g;
-        r.tmpx = (char*)tmpx + (size_t)g * Bg * tmpx_stride;
-        r.normx = normx ? (char*)normx + (size_t)g * Bg * normx_stride : nullptr;
-        hipEvent_t* ev = P->events.data() + (size_t)g * P->n_events;
-        hipEvent_t* pev = prof.on ? prof.ev.data() + (size_t)g * 2 * P->steps.size() : nullptr;
-        for (size_t i = 0; i < P->steps.size(); ++i) {
-            Step& st = P->steps[i];
-            hipStream_t ss = serial ? (hipStream_t)stream : streams[g][st.stream];
-            if (st.kind == S_RECORD) {
-                if (!serial) CHORE_HIP_CHECK(h, hipEventRecord(ev[st.event], ss));
-                continue;
-            }
-            if (st.kind == S_WAIT) {
-                if (!serial) CHORE_HIP_CHECK(h, hipStreamWaitEvent(ss, ev[st.event], 0));
-                continue;
-            }
-            if (st.kind == S_MEMSET) {
-                CHORE_HIP_CHECK(h, hipMemsetAsync(r.stats, 0, P->stats_bytes, ss));
-                continue;
-            }
-            r.s = ss;
-            if (prof.on) CHORE_HIP_CHECK(h, hipEventRecord(pev[2 * i], ss));
-            st.fn(r);
-            if (r.rc) return r.rc;
-            if (prof.on) CHORE_HIP_CHECK(h, hipEventRecord(pev[2 * i + 1], ss));
-            if (debug_sync) {
-                fprintf(stderr, "[chore] group %d step %s\n", g, st.label.c_str());
-                hipError_t e = hipStreamSynchronize(ss);
-                if (e != hipSuccess) CHORE_FAIL(h, CHORE_EHIP, "step '%s' failed: %s", st.label.c_str(), hipGetErrorString(e));
-            }
+    RunCtx r;
+    r.h = h; r.dtype = dtype; r.s = (hipStream_t)stream; r.arena = (const char*)arena;
+    for (int i = 0; i < MAX_STREAMS; ++i) r.pool_base[i] = (char*)workspace + P->pool_off[i];
+    r.stats = (char*)workspace + P->stats_off;
+    r.images = images;
+    r.feats = feat_out;
+    r.tmpx = tmpx;
+    r.normx = normx;
+    for (size_t i = 0; i < P->steps.size(); ++i) {
+        Step& st = P->steps[i];
+        hipStream_t ss = serial ? (hipStream_t)stream : streams[st.stream];
+        if (st.kind == S_RECORD) {
+            if (!serial) CHORE_HIP_CHECK(h, hipEventRecord(P->events[st.event], ss));
+            continue;
         }
-        if (g > 0 && !serial) {   // the caller's stream continues after every group
-            if (!cache->join_ev[g]) CHORE_HIP_CHECK(h, hipEventCreateWithFlags(&cache->join_ev[g], hipEventDisableTiming));
-            CHORE_HIP_CHECK(h, hipEventRecord(cache->join_ev[g], streams[g][0]));
-            CHORE_HIP_CHECK(h, hipStreamWaitEvent((hipStream_t)stream, cache->join_ev[g], 0));
+        if (st.kind == S_WAIT) {
+            if (!serial) CHORE_HIP_CHECK(h, hipStreamWaitEvent(ss, P->events[st.event], 0));
+            continue;
+        }
+        if (st.kind == S_MEMSET) {
+            CHORE_HIP_CHECK(h, hipMemsetAsync(r.stats, 0, P->stats_bytes, ss));
+            continue;
+        }
+        r.s = ss;
+        if (prof.on) CHORE_HIP_CHECK(h, hipEventRecord(prof.ev[2 * i], ss));
+        st.fn(r);
+        if (r.rc) return r.rc;
+        if (prof.on) CHORE_HIP_CHECK(h, hipEventRecord(prof.ev[2 * i + 1], ss));
+        if (debug_sync) {
+            fprintf(stderr, "[chore] step %s\n", st.label.c_str());
+            hipError_t e = hipStreamSynchronize(ss);
+            if (e != hipSuccess) CHORE_FAIL(h, CHORE_EHIP, "step '%s' failed: %s", st.label.c_str(), hipGetErrorString(e));
         }
     }
     if (prof.on) {
         CHORE_HIP_CHECK(h, hipStreamSynchronize((hipStream_t)stream));
-        for (int g = 0; g < G; ++g)
-            for (size_t i = 0; i < P->steps.size(); ++i) {
-                const Step& st = P->steps[i];
-                if (st.kind != S_KERNEL) continue;
-                float ms = 0.f;
-                CHORE_HIP_CHECK(h, hipEventElapsedTime(&ms, prof.ev[(g * P->steps.size() + i) * 2], prof.ev[(g * P->steps.size() + i) * 2 + 1]));
-                prof.ms[st.klass] += ms;
-                prof.flops[st.klass] += st.flops;
-                prof.bytes[st.klass] += st.bytes;
-                prof.launches[st.klass] += 1;
-            }
+        for (size_t i = 0; i < P->steps.size(); ++i) {
+            const Step& st = P->steps[i];
+            if (st.kind != S_KERNEL) continue;
+            float ms = 0.f;
+            CHORE_HIP_CHECK(h, hipEventElapsedTime(&ms, prof.ev[2 * i], prof.ev[2 * i + 1]));
+            prof.ms[st.klass] += ms;
+            prof.flops[st.klass] += st.flops;
+            prof.bytes[st.klass] += st.bytes;
+            prof.launches[st.klass] += 1;
+        }
     }
     return CHORE_OK;
 }

@@ -525,8 +525,7 @@ static int launch_query_bwd_t(chore_handle* h, const QueryArgs& a, hipStream_t s
         }
     }
     if constexpr (!TRAIN) {
-        static const bool x3_small = getenv("CHORE_QUERY_X3_BWD_SMALL") != nullptr;
-        if (query_small_tiles(a.B, a.N) || (X3 && (x3_small || x3_bwd_prefers_small(a.B, a.N))))
+        if (query_small_tiles(a.B, a.N) || (X3 && x3_bwd_prefers_small(a.B, a.N)))
             return launch_query_bwd_n<T, false, 1, X3>(h, a, s);
     }
     // the training variants are bound by their staging stores: measured slower with eight waves (39.4 vs 38.6 ms per step)

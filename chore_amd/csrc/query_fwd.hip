@@ -728,17 +728,19 @@ static int launch_query_fwd_n(chore_handle* h, const QueryArgs& a, hipStream_t s
 // 64-point tiles unless they would leave CUs without a workgroup
 bool query_small_tiles(int B, int N) { return (size_t)B * ((N + QT_PTS - 1) / QT_PTS) <= 256; }
 
-template <typename T, bool X3 = false>
+template <typename T>
 static int launch_query_fwd_w8(chore_handle* h, const QueryArgs& a, hipStream_t s) {
     const size_t smem = sizeof(QueryFwdSmemT<64>);
     dim3 grid((a.N + 63) / 64, a.B);
-    return CHORE_LAUNCH(h, s, (query_fwd_f32_w8_kernel<T, false, X3>), grid, dim3(512), smem, a);
+    return CHORE_LAUNCH(h, s, (query_fwd_f32_w8_kernel<T, false, false>), grid, dim3(512), smem, a);
 }
+
+// CHORE_QUERY_W4=1 (A/B switch): the four-wave kernel where the eight-wave one is the default -- the fp32-MFMA heads' large
+// inference queries (here and in query_bwd.hip) and the training forward
+static bool query_w4() { static const bool v = getenv("CHORE_QUERY_W4") != nullptr; return v; }
 
 template <typename T, bool X3 = false>
 static int launch_query_fwd_t(chore_handle* h, const QueryArgs& a, hipStream_t s) {
-    static const bool w4 = getenv("CHORE_QUERY_W4") != nullptr;     // A/B switches for large queries
-    static const bool w8 = getenv("CHORE_QUERY_W8") != nullptr;
     if constexpr (X3) {
         static const bool nosplit = getenv("CHORE_QUERY_X3_NOSPLIT") != nullptr;      // A/B switch: the one-wave-per-head kernels
         if (!nosplit) return query_small_tiles(a.B, a.N) ? launch_query_fwd_split<T, 1>(h, a, s) : launch_query_fwd_split<T, 2>(h, a, s);
@@ -748,9 +750,9 @@ static int launch_query_fwd_t(chore_handle* h, const QueryArgs& a, hipStream_t s
     // four waves, so the CU holds one whatever the three leaving waves free: 363 against 335 us at 8 x 20 000 points)
     // fp16 x 3: a k-step of MFMAs is 2.7 x shorter than the fp32 one for the same weight bytes, and the eight-wave kernel
     // (both waves of a head fetch the head's fragments) is bound by the L1's 64 B / clk: 0.227 ms against 0.203 ms for
-    // four waves with two column blocks each (4 x 20 000 points)
-    if (X3 ? !w8 : w4) return launch_query_fwd_n<T, 2, X3>(h, a, s);
-    return launch_query_fwd_w8<T, X3>(h, a, s);
+    // four waves with two column blocks each (4 x 20 000 points; the eight-wave fp16 x 3 inference kernel was removed in round 8)
+    if constexpr (X3) return launch_query_fwd_n<T, 2, true>(h, a, s);
+    else return query_w4() ? launch_query_fwd_n<T, 2>(h, a, s) : launch_query_fwd_w8<T>(h, a, s);
 }
 
 template <typename T, bool X3 = false>
@@ -762,7 +764,7 @@ static int launch_query_fwd_train_w8(chore_handle* h, const QueryArgs& a, hipStr
 
 template <typename T, bool X3 = false>
 static int launch_query_fwd_train_t(chore_handle* h, const QueryArgs& a, hipStream_t s) {
-    if (!getenv("CHORE_QUERY_W4")) return launch_query_fwd_train_w8<T, X3>(h, a, s);
+    if (!query_w4()) return launch_query_fwd_train_w8<T, X3>(h, a, s);
     const size_t smem = sizeof(QueryFwdSmemT<64>);
     dim3 grid((a.N + 63) / 64, a.B);
     return CHORE_LAUNCH(h, s, (query_fwd_f32_kernel<T, 2, true, X3>), grid, dim3(256), smem, a);

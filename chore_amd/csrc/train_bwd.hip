@@ -47,9 +47,13 @@ struct WgradArgs {
     float* part_bias;         // [S][Cout] or null
     int S;                    // shares of the pixel tiles
     const unsigned* dy_amax;  // fp16 x 3 kernels: AMAX_CELLS partial maxima of |dy| (enc_common.h), or null
-    int dbg;                  // CHORE_WGRAD_DBG ablation bits (measurements only; results are wrong when set): 1 no MFMAs, 2 no split / LDS
-                              // stores, 4 no global loads
 };
+
+// kernel experiments (scripts/build_variant.sh wgN train_bwd.hip -DWGRAD_DBG=N): ablation bits of the fp16 x 3 weight-gradient
+// kernels -- 1 no MFMAs, 2 no split / LDS stores, 4 no global loads.  Results are wrong when set; the shipped library is built with 0
+#ifndef WGRAD_DBG
+#define WGRAD_DBG 0
+#endif
 
 template <typename T, int TAPS>
 __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs a) {
@@ -456,7 +460,7 @@ __global__ __launch_bounds__(256) void wgrad64_x3_kernel(WgradArgs a) {
             vx[q][0] = p[0]; vx[q][1] = p[1];
         }
     };
-    if (share < tiles && !(a.dbg & 4)) issue_loads(share);
+    if (share < tiles && !(WGRAD_DBG & 4)) issue_loads(share);
     for (int tile = share; tile < tiles; tile += a.S) {
         const int b = tile / (tiles_x * tiles_y), tt = tile % (tiles_x * tiles_y);
         const int ty0 = (tt / tiles_x) * WX_TH, tx0 = (tt % tiles_x) * TW;
@@ -466,7 +470,7 @@ __global__ __launch_bounds__(256) void wgrad64_x3_kernel(WgradArgs a) {
             __syncthreads();
         }
         cur_b = b;
-        if (!(a.dbg & 2)) {
+        if constexpr ((WGRAD_DBG & 2) == 0) {
 #pragma unroll
         for (int q = 0; q < NVY; ++q) {
             const int i = tid + 256 * q, row = i >> 3, v = i & 7;
@@ -500,7 +504,7 @@ __global__ __launch_bounds__(256) void wgrad64_x3_kernel(WgradArgs a) {
         }
         }
         __syncthreads();
-        if (!(a.dbg & 4)) issue_loads(tile + a.S < tiles ? tile + a.S : tile);      // the next tile's operands travel under this tile's MFMAs
+        if constexpr ((WGRAD_DBG & 4) == 0) issue_loads(tile + a.S < tiles ? tile + a.S : tile);      // the next tile's operands travel under this tile's MFMAs
         if (a.part_bias && pair % nbc == 0 && tid < 64) {
             for (int p = 0; p < YROWS; ++p)
                 bias_acc += (float)*(const _Float16*)(imgY + p * W64_PITCH + tid * 2) + (float)*(const _Float16*)(imgY + PLY + p * W64_PITCH + tid * 2);
@@ -508,7 +512,7 @@ __global__ __launch_bounds__(256) void wgrad64_x3_kernel(WgradArgs a) {
         // ---- MFMAs: small terms first, all three into the same accumulator ----
         const char* baseY = imgY + lane_off + coh * 64;
         const char* baseA = imgA + lane_off + cih * 64;
-        if (!(a.dbg & 1)) {
+        if constexpr ((WGRAD_DBG & 1) == 0) {
 #pragma unroll 1
         for (int y = 0; y < WX_TH; ++y) {
 #pragma unroll
@@ -636,7 +640,7 @@ __global__ __launch_bounds__(512) void wgrad64_x3_pc_kernel(WgradArgs a) {
             hi = __builtin_bit_cast(u32x4, hh);
             lo = __builtin_bit_cast(u32x4, ll);
         };
-        if (ntile > 0 && !(a.dbg & 4)) issue_loads(share);
+        if (ntile > 0 && !(WGRAD_DBG & 4)) issue_loads(share);
         for (int it = 0; it < ntile; ++it) {
             const int tile = share + it * a.S;
             const int b = tile / (tiles_x * tiles_y), tt = tile % (tiles_x * tiles_y);
@@ -648,7 +652,7 @@ __global__ __launch_bounds__(512) void wgrad64_x3_pc_kernel(WgradArgs a) {
                 for (int j = 0; j < 8; ++j) gn_scale_shift(a.st, a.B, b, a.Cin, ci0 + v * 8 + j, a.H * a.W, a.gamma, a.beta, sc[j], sh[j]);
                 cur_b = b;
             }
-            if (!(a.dbg & 2)) {
+            if constexpr ((WGRAD_DBG & 2) == 0) {
 #pragma unroll
             for (int q = 0; q < NVY; ++q) {
                 const int row = (ptid + 256 * q) >> 3;
@@ -686,7 +690,7 @@ __global__ __launch_bounds__(512) void wgrad64_x3_pc_kernel(WgradArgs a) {
                 }
             }
             }
-            if (!(a.dbg & 4)) issue_loads(it + 1 < ntile ? tile + a.S : tile);      // in flight across the barrier and the next split
+            if constexpr ((WGRAD_DBG & 4) == 0) issue_loads(it + 1 < ntile ? tile + a.S : tile);      // in flight across the barrier and the next split
             wp_barrier();                                   // barrier `it`: buffer it % 2 is complete
         }
         wp_barrier();                                       // the consumers have read the last buffer: the LDS is free
@@ -716,7 +720,7 @@ __global__ __launch_bounds__(512) void wgrad64_x3_pc_kernel(WgradArgs a) {
             const char* imgA = smem + (it & 1) * BUF;
             const char* baseY = imgA + 2 * PLA + lane_off + coh * 64;
             const char* baseA = imgA + lane_off + cih * 64;
-            if (a.dbg & 1) continue;
+            if constexpr ((WGRAD_DBG & 1) != 0) continue;
 #pragma unroll
             for (int y = 0; y < WP_TH; ++y) {
 #pragma unroll
@@ -823,7 +827,7 @@ __global__ __launch_bounds__(512) void wgrad128_x3_pc_kernel(WgradArgs a) {
             hi = __builtin_bit_cast(u32x4, hh);
             lo = __builtin_bit_cast(u32x4, ll);
         };
-        if (ntile > 0 && !(a.dbg & 4)) issue_loads(share);
+        if (ntile > 0 && !(WGRAD_DBG & 4)) issue_loads(share);
         for (int it = 0; it < ntile; ++it) {
             const int tile = share + it * a.S;
             const int b = (int)(((size_t)tile * W128_PX) / HW);
@@ -834,7 +838,7 @@ __global__ __launch_bounds__(512) void wgrad128_x3_pc_kernel(WgradArgs a) {
                 for (int j = 0; j < 8; ++j) gn_scale_shift(a.st, a.B, b, a.Cin, ci0 + v * 8 + j, HW, a.gamma, a.beta, sc[j], sh[j]);
                 cur_b = b;
             }
-            if (!(a.dbg & 2)) {
+            if constexpr ((WGRAD_DBG & 2) == 0) {
 #pragma unroll
             for (int q = 0; q < NV; ++q) {
                 const int row = prow + (256 / SLOTS) * q;
@@ -860,7 +864,7 @@ __global__ __launch_bounds__(512) void wgrad128_x3_pc_kernel(WgradArgs a) {
                 *(u32x4*)(imgA + PL + row * W128_PITCH + v * 16) = lo;
             }
             }
-            if (!(a.dbg & 4)) issue_loads(it + 1 < ntile ? tile + a.S : tile);      // in flight across the barrier and the next split
+            if constexpr ((WGRAD_DBG & 4) == 0) issue_loads(it + 1 < ntile ? tile + a.S : tile);      // in flight across the barrier and the next split
             wp_barrier();                                       // barrier `it`: buffer it % 2 is complete
         }
         wp_barrier();                                           // the consumers have read the last buffer: the LDS is free
@@ -891,7 +895,7 @@ __global__ __launch_bounds__(512) void wgrad128_x3_pc_kernel(WgradArgs a) {
             const char* imgA = smem + (it & 1) * BUF;
             const char* baseY = imgA + 2 * PL + lane_off + coh * 128;
             const char* baseA = imgA + lane_off + cih * 128;
-            if (a.dbg & 1) continue;
+            if constexpr ((WGRAD_DBG & 1) != 0) continue;
 #pragma unroll
             for (int xb = 0; xb < W128_PX; xb += 16) {
                 tb_f16x8 fyh[2], fyl[2], fxh[2], fxl[2];
@@ -941,8 +945,7 @@ static bool wgrad128_ok(int taps, int B, int H, int W, int Cin, int Cout) {
 static int wgrad128_shares(int B, int H, int W, int Cin, int Cout) {
     const int tiles = (int)((long)B * H * W / W128_PX);
     const int pairs = (Cout / 128) * (Cin / 128);
-    static const int wgs = getenv("CHORE_WGRAD128_WGS") ? atoi(getenv("CHORE_WGRAD128_WGS")) : 256;      // workgroups to aim for (A/B)
-    int S = ((wgs + pairs - 1) / pairs + 7) / 8 * 8;
+    int S = ((256 + pairs - 1) / pairs + 7) / 8 * 8;
     if (S > tiles) S = tiles;
     return S;
 }
@@ -1344,8 +1347,6 @@ int conv2d_bwd_weight_impl(chore_handle* h, int dtype, int taps, const void* x, 
     if (dtype != CHORE_F32 && dtype != CHORE_BF16 && dtype != CHORE_F16X3) CHORE_FAIL(h, CHORE_EINVAL, "chore_conv2d_bwd_weight: bad dtype");
     WgradArgs a;
     a.dy_amax = dy_amax;
-    static const int wdbg = getenv("CHORE_WGRAD_DBG") ? atoi(getenv("CHORE_WGRAD_DBG")) : 0;
-    a.dbg = wdbg;
     a.x = x; a.st = (const GroupStat*)stats; a.gamma = gamma; a.beta = beta; a.dy = dy;
     a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
     a.xs = Cin; a.ys = dy_stride; a.npix = (long long)B * H * W;
@@ -1466,7 +1467,7 @@ int chore_gemm_tn_f32(chore_handle* h, const float* A, int lda, const float* B, 
         CHORE_FAIL(h, CHORE_EINVAL, "chore_gemm_tn_f32: M, N must be multiples of 32 (P=%d M=%d N=%d)", P, M, N);
     hipStream_t s = (hipStream_t)stream;
     WgradArgs a;
-    a.dy_amax = nullptr; a.dbg = 0;
+    a.dy_amax = nullptr;
     a.x = B; a.st = nullptr; a.gamma = nullptr; a.beta = nullptr; a.dy = A;
     a.B = 1; a.H = (P + 31) / 32; a.W = 32; a.Cin = N; a.Cout = M; a.xs = ldb; a.ys = lda; a.npix = P;
     a.S = wgrad_shares(1, a.H, a.W, N, M);

@@ -128,7 +128,7 @@ class ReconFitterBehave(ReconFitterBase):
     fuse_stop_rule = True      # the steps' loss is sum_dict's result as it comes: the stop rule rides in that launch (graph_step)
 
     def _stepper(self, *a, **k):
-        k.setdefault("fuse_rule", self.fuse_stop_rule and not os.environ.get("CHORE_FIT_SPLIT_RULE"))
+        k.setdefault("fuse_rule", self.fuse_stop_rule)
         if self.use_graphs:
             gate = self.__dict__.get("_gate")
             if gate is None:
@@ -374,8 +374,6 @@ class ReconFitterBehave(ReconFitterBase):
         issued: a capture does not tolerate another thread's allocations."""
         import copy
         from concurrent.futures import ThreadPoolExecutor
-        if self._seed() is None:
-            self._pipe_seed = int(torch.initial_seed() % (1 << 31))
         dev = torch.device(self.device)
         main = torch.cuda.current_stream(dev)
         state = self.__dict__.get("_pipe_state")
@@ -384,7 +382,6 @@ class ReconFitterBehave(ReconFitterBase):
             nets = [generator.model, copy.copy(generator.model)]
             gens = [generator, copy.copy(generator)]
             gens[1].model = nets[1]
-            prio = int(os.environ.get("CHORE_PIPE_PRIO", "0"))
             # ONE worker thread for the fitter's lifetime (it owns a C handle of its own, chore_amd/_lib.py: a thread per call would
             # leave a handle behind per call)
             # CHORE_PIPE_CUS=n: the preparation streams run on n of the compute units (the same share of every XCD), the rest stay
@@ -394,7 +391,7 @@ class ReconFitterBehave(ReconFitterBase):
                 from chore_amd import _lib
                 prep_streams = [_lib.cu_masked_stream(dev.index or 0, cus) for _ in range(2)]
             else:
-                prep_streams = [torch.cuda.Stream(dev, priority=prio), torch.cuda.Stream(dev, priority=prio)]
+                prep_streams = [torch.cuda.Stream(dev), torch.cuda.Stream(dev)]     # (priority -1 measured slower)
             state = self._pipe_state = (generator, nets, gens, prep_streams,
                                         [False, False], ThreadPoolExecutor(max_workers=1, thread_name_prefix="chore-prep"))
         _, nets, gens, streams, warm, pool = state      # warm[s]: slot s's inner steps are recorded (kept across calls with the slots)
@@ -442,12 +439,17 @@ class ReconFitterBehave(ReconFitterBase):
             ready.record(main)
             return pool.submit(prepare, k, ready)
 
+        seeded = self._seed() is None      # a direct call: the seed lasts for this call only, as in fit_recon
+        if seeded:
+            self._pipe_seed = int(torch.initial_seed() % (1 << 31))
         gate.enter()
         try:
             self._fit_pipelined_loop(todo, submit, pool, warm, main, last_read, finish, smpl_iters, object_iters, dbg, t_base)
         finally:
             gate.leave()
             self._gate = None
+            if seeded:
+                self._pipe_seed = None
         if dbg:
             torch.cuda.synchronize()
             ref = [d for d in dbg if d[0] == "opt"][0][4]
@@ -498,11 +500,9 @@ class ReconFitterBehave(ReconFitterBase):
         tolerate another thread's allocations or synchronisations.  `finish` is called by the calling thread in loader order."""
         import copy
         from concurrent.futures import ThreadPoolExecutor
-        if self._seed() is None:
-            self._pipe_seed = int(torch.initial_seed() % (1 << 31))
         dev = torch.device(self.device)
         main = torch.cuda.current_stream(dev)
-        nch = max(2, int(os.environ.get("CHORE_FIT_CHAINS", self.chains)))
+        nch = max(2, int(self.chains))
         state = self.__dict__.get("_chain_state")
         if state is None or state["generator"] is not generator or state["nets"][0] is not generator.model or len(state["nets"]) != nch:
             nets = [generator.model] + [copy.copy(generator.model) for _ in range(nch - 1)]
@@ -530,8 +530,11 @@ class ReconFitterBehave(ReconFitterBase):
                 gate.leave()
             return fitted, done
 
+        seeded = self._seed() is None      # a direct call: the seed lasts for this call only, as in fit_recon
+        if seeded:
+            self._pipe_seed = int(torch.initial_seed() % (1 << 31))
+        futs = []
         try:
-            futs = []
             for k in range(len(todo)):                             # each slot's executor runs its batches in order
                 ready = torch.cuda.Event()
                 ready.record(main)
@@ -557,6 +560,8 @@ class ReconFitterBehave(ReconFitterBase):
                 except Exception:
                     pass
             self._gate = None
+            if seeded:
+                self._pipe_seed = None
 
     batch_ends = None     # a list: one timing event per finished batch of fit_recon (serial or pipelined) is appended
 
@@ -748,32 +753,13 @@ class ReconFitterBehave(ReconFitterBase):
                 df_hum_o = model.get_preds()[0][:, 1, :]
             else:
                 df_hum_o = const["df_hum_o"]
-            # The collision term needs nothing of the contact term and both are chains of small launches.  CHORE_FIT_TWO_STREAMS=1
-            # runs them side by side (fork / join; inside a recorded step = two branches of the graph): 0.280 -> 0.273 ms per
-            # iteration, measured.  Off by default: gradients then cross streams inside autograd, whose tensors the caching
-            # allocator hands back to the stream that made them -- not worth 2.6 % before that is audited.
-            side = None
-            if self.scan_faces is not None and object.is_cuda and os.environ.get("CHORE_FIT_TWO_STREAMS"):
-                cur = torch.cuda.current_stream(object.device)
-                side = self._side_stream(object.device)
-                side.wait_stream(cur)
-                with torch.cuda.stream(side):
-                    collide = self.compute_collision_loss(smpl_verts, smpl.faces, R, obj_t, obj_s)
+            # (The collision term needs nothing of the contact term; the two side by side on two streams measured 0.280 -> 0.273 ms
+            # per iteration.  Removed in round 8: gradients then cross streams inside autograd, whose tensors the caching allocator
+            # hands back to the stream that made them -- not worth 2.6 %.)
             self.compute_contact_loss(df_hum_o, df_obj_h, object, smpl_verts, loss_dict, part_o=part_o)
-            if side is not None:
-                cur = torch.cuda.current_stream(object.device)
-                cur.wait_stream(side)
-                collide.record_stream(cur)
-                loss_dict["collide"] = collide
-            elif self.scan_faces is not None:
+            if self.scan_faces is not None:
                 loss_dict["collide"] = self.compute_collision_loss(smpl_verts, smpl.faces, R, obj_t, obj_s)
         return loss_dict
-
-    def _side_stream(self, device):
-        st = getattr(self, "_side", None)
-        if st is None or st.device != device:
-            st = self._side = torch.cuda.Stream(device)
-        return st
 
     def optimize_smpl_object(self, model, data_dict, obj_iter=20, joint_iter=10, steps_per_iter=10, sil_iter=50,
                              max_iter=100):

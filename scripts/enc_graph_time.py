@@ -1,4 +1,5 @@
-"""times CHORE.filter (B = 4 x 512 x 512) issued eagerly and replayed from a hipGraph, for the batch-group counts in argv"""
+"""times CHORE.filter (B = 4 x 512 x 512) issued eagerly and replayed from a hipGraph.
+usage: python scripts/enc_graph_time.py [fp16x3|bf16|fp16|fp32]"""
 import os, sys, time, torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, REPO)
 from bench import chore_opt
@@ -28,4 +29,4 @@ with torch.no_grad():
             net.filter(img)
     torch.cuda.synchronize()
     graph = timeit(g.replay)
-print("groups %s: eager %.3f ms (host enqueue %.3f ms), graph replay %.3f ms" % (os.environ.get("CHORE_ENC_GROUPS", "default"), eager, host, graph))
+print("%s: eager %.3f ms (host enqueue %.3f ms), graph replay %.3f ms" % (dt, eager, host, graph))

@@ -20,22 +20,16 @@ dtm = torch.empty(B, 256, 256, 64, device=dev)
 
 def run(name, pts, tm=False):
     points = torch.from_numpy(pts.astype(np.float32)).to(dev)
-    for scan in (0, 1):
-        if scan:
-            os.environ["CHORE_SCATTER_SCAN"] = "1"
-        else:
-            os.environ.pop("CHORE_SCATTER_SCAN", None)
-        call = lambda: _lib.check(_lib.lib.chore_scatter_features(h, points.data_ptr(), cc.data_ptr(), B, N, 128, 128, 256, 256, cam6,
-                                                                  staging.data_ptr(), dfe.data_ptr(), dtm.data_ptr() if tm else None, 0, stream), h, "s")
-        for _ in range(3):
-            call()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize(); e0.record()
-        for _ in range(20):
-            call()
-        e1.record(); torch.cuda.synchronize()
-        print("%-34s %s  %.1f us / call" % (name, "scan  " if scan else "binned", e0.elapsed_time(e1) / 20 * 1e3))
-
+    call = lambda: _lib.check(_lib.lib.chore_scatter_features(h, points.data_ptr(), cc.data_ptr(), B, N, 128, 128, 256, 256, cam6,
+                                                              staging.data_ptr(), dfe.data_ptr(), dtm.data_ptr() if tm else None, 0, stream), h, "s")
+    for _ in range(3):
+        call()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize(); e0.record()
+    for _ in range(20):
+        call()
+    e1.record(); torch.cuda.synchronize()
+    print("%-34s %.1f us / call" % (name, e0.elapsed_time(e1) / 20 * 1e3))
 
 p = synth.synth_points(B, N, seed=1)
 run("bench points (17 % inside)", p)

@@ -1,6 +1,8 @@
 """weight gradient of every convolution layer shape of the encoder at B = 4 x 512^2 through chore_conv2d_bwd_weight (GroupNorm + ReLU
 recomputed while staging): median us per call (partial sums + the ordered finish launch).
-usage: python scripts/wgrad_layer_ab.py fp16x3|bf16|fp32   (CHORE_WGRAD_DBG=<bits> ablates phases of wgrad64_x3_kernel)"""
+usage: python scripts/wgrad_layer_ab.py fp16x3|bf16|fp32
+Phase ablations of the fp16 x 3 kernels are a build variant (scripts/build_variant.sh wgN train_bwd.hip -DWGRAD_DBG=N: 1 no MFMAs,
+2 no split / LDS stores, 4 no global loads; results are wrong then), loaded with CHORE_HIP_LIB=<that library>."""
 import json
 import sys
 
