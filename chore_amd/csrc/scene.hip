@@ -1,0 +1,162 @@
+// scene.hip -- triangles and points in one image: chore_render_fwd's face layer and chore_splat_fwd's point layer, depth-tested
+// against each other per SAMPLE and only then resolved.  Forward only, for the fit's debug views.
+//
+// The two existing rasterisers resolve their own super-sampling, so their outputs cannot be composited: a silhouette pixel
+// is a mixture there and its depth test is lost.  Here nothing new decides a winner: the passes are render.hip's setup and
+// binning (render_common.h) and splat.hip's point pass into the 64-bit keys (splat_common.h), unchanged, so each layer is
+// bit-identical to the kernel it comes from.  scene_tile_kernel is render_tile_kernel's walk with the winner in
+// registers; after the walk the lane loads the keys of its own SS x SS samples (at SS = 2 one 16-byte load per sample row),
+// shades both layers with the shared expressions, composes by the rule in include/chore_hip.h, resolves and stores.  The
+// super-sampled layers never reach memory.
+//   * two layers only: a translucent face shows the nearest point behind it or the background, never another face.
+//   * the call is a clear kernel (keys = empty, bin counters = 0; no hipMemsetAsync, whose byte-memset nodes replay
+//     unreliably in hipGraphs, see splat.hip), the setup kernel, the point pass and the tile kernel, all on the caller's
+//     stream; nothing is allocated or read back, so it can be captured.
+//   * workspace: render.hip's workspace, padded to 256 bytes, then the keys.
+#include "render_common.h"
+#include "splat_common.h"
+
+namespace {
+
+// keys[0, nkeys) = SP_EMPTY (16-byte stores where a pair is whole) and count[0, ncount) = 0, in one grid
+__global__ __launch_bounds__(256) void scene_clear_kernel(unsigned long long* __restrict__ keys, size_t nkeys,
+                                                          int* __restrict__ count, size_t ncount) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (2 * i + 1 < nkeys)
+        reinterpret_cast<ulonglong2*>(keys)[i] = make_ulonglong2(SP_EMPTY, SP_EMPTY);
+    else if (2 * i < nkeys)
+        keys[2 * i] = SP_EMPTY;
+    if (i < ncount) count[i] = 0;
+}
+
+template <int SS>
+__global__ __launch_bounds__(256) void scene_tile_kernel(const TriSetup* __restrict__ ts, const int* __restrict__ count,
+                                                         const int* __restrict__ list, const float* __restrict__ textures,
+                                                         const float* __restrict__ light, const float* __restrict__ face_opacity,
+                                                         int F, int tsz, const unsigned long long* __restrict__ keys,
+                                                         const float* __restrict__ pts, const float* __restrict__ colors,
+                                                         const float* __restrict__ radius, float radius_px, int N, float bias,
+                                                         int size, float ambient, float near, float far, float tex_eps,
+                                                         float bg0, float bg1, float bg2, float* __restrict__ rgb,
+                                                         float* __restrict__ depth_out, float* __restrict__ alpha_out,
+                                                         int* __restrict__ sample_id) {
+    constexpr int NS = SS * SS;
+    __shared__ RbShared sh;
+    const int S = size * SS;
+    const int b = blockIdx.z;
+    const TriSetup* tsb = ts + (size_t)b * F;
+    int px, py;
+    bool inside;
+    float zb[NS], wb[NS][3];
+    int best[NS];
+    rb_walk<SS>(sh, ts, count, list, F, size, near, far, px, py, inside, zb, wb, best);
+    if (!inside) return;
+
+    unsigned long long k[NS];
+    sp_load_keys<SS>(keys + (size_t)b * S * S, S, px, py, k);
+    const float Sf = (float)S;
+    const float direct = __fsub_rn(1.f, ambient);
+    float acc[3] = {0.f, 0.f, 0.f}, zacc = 0.f, aacc = 0.f;
+    int id[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        float c[3] = {bg0, bg1, bg2}, z = far, a = 0.f;
+        id[s] = -1;
+        const bool pt = k[s] != SP_EMPTY;
+        if (pt) {                       // `c` becomes the point's colour: what shows if it is in front, and under a face if not
+            const unsigned n = (unsigned)k[s];
+            sp_shade(pts, colors, radius, radius_px, SS, Sf, near, far, (size_t)b * N + n, px * SS + (s % SS),
+                     py * SS + (s / SS), ambient, direct, c, z);
+            a = 1.f;
+            id[s] = -2 - (int)n;
+        }
+        // equality goes to the face
+        if (best[s] >= 0 && !(pt && __fsub_rn(z, bias) < zb[s])) {
+            float m[3];
+            rb_shade(tsb, textures, light, b, F, best[s], tsz, tex_eps, wb[s], zb[s], m);
+            float o = 1.f;
+            if (face_opacity) o = fminf(fmaxf(face_opacity[(size_t)b * F + best[s]], 0.f), 1.f);     // NaN -> 0
+            if (o >= 1.f) {
+#pragma unroll
+                for (int q = 0; q < 3; ++q) c[q] = m[q];
+            } else {
+                const float u = __fsub_rn(1.f, o);
+#pragma unroll
+                for (int q = 0; q < 3; ++q) c[q] = __fadd_rn(__fmul_rn(o, m[q]), __fmul_rn(u, c[q]));
+            }
+            z = zb[s];
+            a = pt ? 1.f : o;
+            id[s] = best[s];
+        }
+#pragma unroll
+        for (int q = 0; q < 3; ++q) acc[q] += c[q];
+        zacc += z;
+        aacc += a;
+    }
+    constexpr float inv_ns = 1.f / NS;
+    const int row = size - 1 - py;                        // the flip of chore_render_fwd
+    const size_t plane = (size_t)size * size, o = (size_t)row * size + px;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) rgb[((size_t)b * 3 + q) * plane + o] = acc[q] * inv_ns;
+    depth_out[(size_t)b * plane + o] = zacc * inv_ns;
+    alpha_out[(size_t)b * plane + o] = aacc * inv_ns;
+    if (sample_id) {
+#pragma unroll
+        for (int s = 0; s < NS; ++s)
+            sample_id[((size_t)b * S + (py * SS + s / SS)) * S + (px * SS + s % SS)] = id[s];
+    }
+}
+
+}  // namespace
+
+extern "C" size_t chore_scene_workspace_bytes(int B, int F, int N, int size, int ssaa) {
+    const size_t rb = render_ws_bytes(B, F, size, ssaa);
+    if (rb == 0 || !render_shape_ok(B, F, 2, size, ssaa) || !splat_shape_ok(B, N, size, ssaa)) return 0;
+    return rb_align(rb) + splat_key_bytes(B, size, ssaa);
+}
+
+extern "C" int chore_scene_fwd(chore_handle* h, const float* tri, const float* textures, const float* light,
+                               const float* face_opacity, int B, int F, int ts, const float* pts, const float* point_rgb,
+                               const float* radius, float radius_px, int N, float point_depth_bias, int size, int ssaa,
+                               float ambient, float near_z, float far_z, float tex_eps, const float* background3, float* rgb,
+                               float* depth, float* alpha, int* sample_id, void* workspace, chore_stream_t stream) {
+    CHORE_ENTER(h);
+    if (!tri || !textures || !pts || !background3 || !rgb || !depth || !alpha || !workspace)
+        CHORE_FAIL(h, CHORE_EINVAL, "chore_scene_fwd: null argument");
+    if (ssaa != 1 && ssaa != 2) CHORE_FAIL(h, CHORE_EINVAL, "chore_scene_fwd: ssaa must be 1 or 2, got %d", ssaa);
+    if (!render_shape_ok(B, F, ts, size, ssaa) || !splat_shape_ok(B, N, size, ssaa))
+        CHORE_FAIL(h, CHORE_EINVAL, "chore_scene_fwd: bad sizes B=%d F=%d ts=%d N=%d size=%d ssaa=%d", B, F, ts, N, size, ssaa);
+    if (!(ambient >= 0.f && ambient <= 1.f))
+        CHORE_FAIL(h, CHORE_EINVAL, "chore_scene_fwd: ambient must lie in [0, 1], got %g", (double)ambient);
+    if (!(near_z < far_z))
+        CHORE_FAIL(h, CHORE_EINVAL, "chore_scene_fwd: near_z %g must be below far_z %g", (double)near_z, (double)far_z);
+    if (!radius && !(radius_px > 0.f))
+        CHORE_FAIL(h, CHORE_EINVAL, "chore_scene_fwd: radius_px must be positive without per-point radii, got %g",
+                   (double)radius_px);
+    if (!(point_depth_bias >= 0.f))
+        CHORE_FAIL(h, CHORE_EINVAL, "chore_scene_fwd: point_depth_bias must be >= 0, got %g", (double)point_depth_bias);
+    hipStream_t s = (hipStream_t)stream;
+    const int S = size * ssaa, nb = rb_bins(S), total = B * N, nf = B * F;
+    const RenderWs w = render_ws(workspace, B, F, S);
+    unsigned long long* keys = (unsigned long long*)((char*)workspace + rb_align(render_ws_bytes(B, F, size, ssaa)));
+    const size_t nkeys = (size_t)B * S * S, ncount = (size_t)B * nb * nb;
+    const size_t nclear = (nkeys + 1) / 2 > ncount ? (nkeys + 1) / 2 : ncount;  // a thread clears two keys and one counter
+    hipLaunchKernelGGL(scene_clear_kernel, dim3((unsigned)((nclear + 255) / 256)), dim3(256), 0, s, keys, nkeys, w.count, ncount);
+    CHORE_LAUNCH_CHECK(h, s);
+    hipLaunchKernelGGL(render_setup_kernel, dim3((nf + 255) / 256), dim3(256), 0, s, tri, B, F, S, w.ts, w.count, w.list);
+    CHORE_LAUNCH_CHECK(h, s);
+    hipLaunchKernelGGL(splat_kernel, dim3((total + SP_BLOCK - 1) / SP_BLOCK), dim3(SP_BLOCK), 0, s, pts, radius, radius_px, total, N, S,
+                       ssaa, near_z, far_z, keys);
+    CHORE_LAUNCH_CHECK(h, s);
+    const dim3 grid((size + RB_TW - 1) / RB_TW, (size + RB_TH - 1) / RB_TH, B);
+    if (ssaa == 2)
+        hipLaunchKernelGGL(scene_tile_kernel<2>, grid, dim3(256), 0, s, w.ts, w.count, w.list, textures, light, face_opacity, F, ts,
+                           keys, pts, point_rgb, radius, radius_px, N, point_depth_bias, size, ambient, near_z, far_z, tex_eps,
+                           background3[0], background3[1], background3[2], rgb, depth, alpha, sample_id);
+    else
+        hipLaunchKernelGGL(scene_tile_kernel<1>, grid, dim3(256), 0, s, w.ts, w.count, w.list, textures, light, face_opacity, F, ts,
+                           keys, pts, point_rgb, radius, radius_px, N, point_depth_bias, size, ambient, near_z, far_z, tex_eps,
+                           background3[0], background3[1], background3[2], rgb, depth, alpha, sample_id);
+    CHORE_LAUNCH_CHECK(h, s);
+    return CHORE_OK;
+}

@@ -550,6 +550,10 @@ class ReconFitterBase:
     VIEW_GREEN, VIEW_RED, VIEW_YELLOW, VIEW_BLUE = (0., 1., 0.), (1., 0., 0.), (1., 1., 0.), (0., 0., 1.)
     VIEW_CYAN, VIEW_MAGENTA = (0., 1., 1.), (1., 0., 1.)
     VIEW_VERT_R, VIEW_POINT_R = 0.005, 0.008      # world radii of SMPL vertices and of generated points, metres
+    # visualize_fit_scene: opacity of the fitted meshes and of the ground-truth meshes, and how far (metres) a point may lie
+    # behind a surface and still be drawn in front of it -- the generated points lie ON the surfaces they were fitted to
+    VIEW_MESH_OPACITY, VIEW_GT_OPACITY, VIEW_POINT_BIAS = 0.6, 0.35, 0.02
+    VIEW_CENTRE_R = 0.06                          # the centre markers of visualize_fit_scene: sphere meshes, metres
     _view_index = 0
     debug_dest = None                             # (save_name, test_id) of the debug files; fit_recon sets it from its args
 
@@ -612,6 +616,66 @@ class ReconFitterBase:
                 colors.append(colour)
                 radii.append(0.06)
         return self._cloud_views(data_dict, smpl, clouds, colors, radii)
+
+    def visualize_fit_scene(self, data_dict, object_verts, smpl, smpl_verts):
+        """[:442-511, 749-795 in one view] the fitted meshes WITH the clouds they were fitted to, occluding each other per
+        sample (chore_scene_fwd through utils/render_utils.render_scene_views): the fitted SMPL mesh and the object template
+        under the fitted pose (`object_verts` (B,V,3) with self.scan_faces) in SMPL_OBJ_COLOR_LIST's colours, translucent;
+        the generator's human points (part colours) and object points (red); contact vertices (blue, from `contact_mask_h`);
+        the centres `obj_center_pred` (cyan), `smpl_center_pred` (yellow), `smpl_center_act` (magenta) as opaque 6 cm sphere
+        meshes; `hum_gt` / `obj_gt` (objects with verts_list() / faces_list(), as the reference reads them) white and more
+        translucent; the keypoints -> (512, 1152, 3) uint8.
+        A translucent face never shows another face, so a centre sphere inside a fitted mesh -- where the centres of a good
+        fit lie -- is hidden by it.  Each centre is therefore ALSO a disc of the same radius at the centre's depth: a point, which
+        the translucent mesh in front of it does show (blended), and which its own sphere covers wherever the sphere is visible."""
+        from ..utils.render_utils import (CLOUD_VIEW_SIZE, SMPL_OBJ_COLOR_LIST, Mesh, icosphere_mesh, render_scene_views)
+        idx = self._view_index
+        host = lambda x: np.asarray(x.detach().cpu()) if torch.is_tensor(x) else np.asarray(x)     # noqa: E731
+        meshes, mesh_colors, opacity = [], [], []
+        if smpl.faces is not None:
+            meshes.append(Mesh(v=host(smpl_verts[idx]), f=host(smpl.faces)))
+            mesh_colors.append(SMPL_OBJ_COLOR_LIST[0])
+            opacity.append(self.VIEW_MESH_OPACITY)
+        if object_verts is not None and self.scan_faces is not None:
+            meshes.append(Mesh(v=host(object_verts[idx]), f=host(self.scan_faces)))
+            mesh_colors.append(SMPL_OBJ_COLOR_LIST[1])
+            opacity.append(self.VIEW_MESH_OPACITY)
+        for key in ("hum_gt", "obj_gt"):
+            if data_dict.get(key) is not None:
+                meshes.append(Mesh(v=host(data_dict[key].verts_list()[idx]), f=host(data_dict[key].faces_list()[idx])))
+                mesh_colors.append((1., 1., 1.))
+                opacity.append(self.VIEW_GT_OPACITY)
+        for key, colour in (("obj_center_pred", self.VIEW_CYAN), ("smpl_center_pred", self.VIEW_YELLOW),
+                            ("smpl_center_act", self.VIEW_MAGENTA)):
+            if key in data_dict:
+                meshes.append(icosphere_mesh(host(data_dict[key][idx]).reshape(3), self.VIEW_CENTRE_R))
+                mesh_colors.append(colour)
+                opacity.append(1.0)
+        clouds, colors, radii = [], [], []
+        for key, colour in (("obj_center_pred", self.VIEW_CYAN), ("smpl_center_pred", self.VIEW_YELLOW),
+                            ("smpl_center_act", self.VIEW_MAGENTA)):
+            if key in data_dict:
+                clouds.append(data_dict[key][idx].detach().reshape(1, 3))
+                colors.append(colour)
+                radii.append(self.VIEW_CENTRE_R)
+        if "contact_mask_h" in data_dict and bool(data_dict["contact_mask_h"][idx].any()):
+            clouds.append(smpl_verts[idx, data_dict["contact_mask_h"][idx]].detach())
+            colors.append(self.VIEW_BLUE)
+            radii.append(self.VIEW_POINT_R)
+        parts = data_dict["part_colors"][idx] if "part_colors" in data_dict else \
+            self.get_parts_colors(data_dict["human_parts"])[idx]
+        clouds += [data_dict["human_init"][idx].detach(), data_dict["obj_init"][idx].detach()]
+        colors += [np.asarray(parts), self.VIEW_RED]
+        radii += [self.VIEW_POINT_R, self.VIEW_POINT_R]
+        crop_center = data_dict["query_dict"]["crop_center"]
+        with torch.no_grad():
+            J, _, _ = smpl.get_landmarks()
+            pxy = self.project_points(J, crop_center)[idx, :, :2] * (CLOUD_VIEW_SIZE / float(self.net_in_size))
+        markers = [(pxy, self.VIEW_YELLOW, 3.0)]              # projected body-25 joints
+        if "body_kpts" in data_dict:                          # detected keypoints
+            markers.append((data_dict["body_kpts"][idx][:, :2] * (CLOUD_VIEW_SIZE / float(self.net_in_size)), self.VIEW_RED, 2.0))
+        return render_scene_views(data_dict["images"][idx], crop_center[idx], meshes, mesh_colors, opacity, clouds, colors, radii,
+                                  markers, point_depth_bias=self.VIEW_POINT_BIAS, camera=self.camera)
 
     def _contact_view_data(self, data_dict, model, obj_center_pred, object, smpl, smpl_verts):
         """what visualize_contact_fitting adds to data_dict for the whole batch: the contact masks (two field queries) and the
@@ -698,7 +762,7 @@ class ReconFitterBase:
             smpl.forget()
 
     def debug_after_object(self, prep, data_dict, smpl, obj_R, obj_t, obj_s):
-        """after optimize_smpl_object: k{tid}.debug_object.png per frame"""
+        """after optimize_smpl_object: k{tid}.debug_object.png and k{tid}.debug_fit.png (visualize_fit_scene) per frame"""
         if not self._debug_on():
             return
         from ..utils.render_utils import write_png
@@ -720,6 +784,13 @@ class ReconFitterBase:
                 for i, f in enumerate(self._debug_files(paths, "object")):
                     self._view_index = i
                     write_png(f, self.visualize_fitting(dd, object, smpl, verts))
+                scan = None
+                if self.scan_verts is not None and self.scan_faces is not None:
+                    scan = self.transform_obj_verts(self.scan_verts.unsqueeze(0).expand(obj_R.shape[0], -1, -1).contiguous(),
+                                                    self.decopose_axis(obj_R.detach(), no_rand=True), obj_t.detach(), obj_s.detach())
+                for i, f in enumerate(self._debug_files(paths, "fit")):
+                    self._view_index = i
+                    write_png(f, self.visualize_fit_scene(dd, scan, smpl, verts))
         finally:
             self._view_index = 0
             model.preds, model.points, model.intermediate_preds_list = kept

@@ -194,6 +194,85 @@ def splat_points(points_ndc, colors=None, radius=2.0, image_size=256, anti_alias
     return out
 
 
+def rasterize_scene(faces, textures, light, points_ndc, colors=None, radius=2.0, face_opacity=None, point_depth_bias=0.0,
+                    image_size=256, anti_aliasing=True, near=DEFAULT_NEAR, far=DEFAULT_FAR, eps=DEFAULT_EPS, ambient=0.6,
+                    background_color=(0, 0, 0), return_index=False):
+    """meshes and point clouds in ONE image, depth-tested against each other per sample before the anti-aliasing average
+    (chore_scene_fwd; the rule is written down in include/chore_hip.h).  faces / textures / light as `rasterize_rgbad` takes
+    them, points_ndc / colors / radius as `splat_points` does; face_opacity (B,F) in [0,1] or None = opaque: a translucent face
+    shows the nearest point behind it or the background, never another face; point_depth_bias >= 0 (depth units) lets a point
+    that lies ON a surface win against it.
+    -> dict(rgb (B,3,S,S), depth (B,S,S), alpha (B,S,S)[, sample_id (B,S*ssaa,S*ssaa) int32, rows not flipped: f >= 0 a face,
+    -2 - n a point, -1 nothing]).  F == 0 is `splat_points`; N == 0 is `rasterize_rgbad` when every face is opaque, and the
+    scene kernel with one point that is never drawn when there is a face_opacity to honour."""
+    if not faces.is_cuda or not points_ndc.is_cuda:
+        raise RuntimeError("chore_amd needs device tensors (no CPU path)")
+    bias = float(point_depth_bias)
+    if not bias >= 0.0:
+        raise ValueError("point_depth_bias must be >= 0, got %r" % (point_depth_bias,))
+    dev = faces.device
+    tri = faces.detach().float().contiguous()
+    pts = points_ndc.detach().to(dev).float().contiguous()
+    if pts.dim() != 3 or pts.shape[2] != 3:
+        raise ValueError("points_ndc (B,N,3) expected, got %s" % (tuple(pts.shape),))
+    if tri.dim() != 4 or pts.shape[0] != tri.shape[0]:
+        raise ValueError("faces (B,F,3,3) and points_ndc (B,N,3) of one batch size expected, got %s and %s"
+                         % (tuple(tri.shape), tuple(pts.shape)))
+    B, Fn, N = tri.shape[0], tri.shape[1], pts.shape[1]
+    if Fn == 0:
+        out = splat_points(pts, colors, radius, image_size, anti_aliasing, near, far, ambient, background_color, return_index)
+        if return_index:
+            pim = out.pop("point_index")
+            out["sample_id"] = torch.where(pim >= 0, -2 - pim, pim)
+        return out
+    if N == 0 and face_opacity is not None:        # z == far is skipped by the point rule
+        pts, colors, radius, N = torch.tensor([0.0, 0.0, float(far)], device=dev).expand(B, 1, 3).contiguous(), None, 1.0, 1
+    if N == 0:
+        out = rasterize_rgbad(tri, textures, light, image_size, anti_aliasing, near, far, eps, background_color, return_index)
+        if return_index:
+            out["sample_id"] = out.pop("face_index")
+        return out
+    tex = textures.detach().to(dev).float().contiguous()
+    ts = tex.shape[2]
+    if tuple(tri.shape) != (B, Fn, 3, 3) or tuple(tex.shape) != (B, Fn, ts, ts, ts, 3):
+        raise ValueError("faces (B,F,3,3) and textures (B,F,ts,ts,ts,3) expected, got %s and %s" % (tuple(tri.shape), tuple(tex.shape)))
+
+    def opt(x, shape, what):
+        if x is None:
+            return None
+        x = x.detach().to(dev).float().contiguous()
+        if tuple(x.shape) != shape:
+            raise ValueError("%s %s expected, got %s" % (what, shape, tuple(x.shape)))
+        return x
+    lt, col = opt(light, (B, Fn, 3), "light"), opt(colors, (B, N, 3), "colors")
+    op = opt(face_opacity, (B, Fn), "face_opacity")
+    rad, radius_px = None, 0.0
+    if torch.is_tensor(radius) and radius.dim() > 0:
+        rad = opt(radius, (B, N), "radius: a number or")
+    else:
+        radius_px = float(radius)
+    ssaa, S = (2 if anti_aliasing else 1), int(image_size)
+    h = _lib.handle(dev.index or 0)
+    nbytes = _lib.lib.chore_scene_workspace_bytes(B, Fn, N, S, ssaa)
+    if nbytes == 0:
+        raise ValueError("unsupported scene shape B=%d F=%d N=%d image_size=%d ssaa=%d" % (B, Fn, N, S, ssaa))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    rgb = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
+    depth = torch.empty(B, S, S, dtype=torch.float32, device=dev)
+    alpha = torch.empty(B, S, S, dtype=torch.float32, device=dev)
+    sid = torch.empty(B, S * ssaa, S * ssaa, dtype=torch.int32, device=dev) if return_index else None
+    bg = (ctypes.c_float * 3)(*[float(c) for c in background_color])
+    ptr = lambda x: x.data_ptr() if x is not None else None      # noqa: E731
+    _lib.check(_lib.lib.chore_scene_fwd(h, tri.data_ptr(), tex.data_ptr(), ptr(lt), ptr(op), B, Fn, ts, pts.data_ptr(), ptr(col),
+                                        ptr(rad), radius_px, N, bias, S, ssaa, float(ambient), float(near), float(far),
+                                        float(eps), bg, rgb.data_ptr(), depth.data_ptr(), alpha.data_ptr(), ptr(sid),
+                                        ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), h, "chore_scene_fwd")
+    out = {"rgb": rgb, "depth": depth, "alpha": alpha}
+    if return_index:
+        out["sample_id"] = sid
+    return out
+
+
 def world_radius_to_pixels(world_radius, z, focal_px):
     """pixel radius of a sphere of `world_radius` metres at depth z under a focal length of `focal_px` OUTPUT pixels:
     focal_px * world_radius / z, so points shrink with distance"""
@@ -263,7 +342,10 @@ class Renderer(nn.Module):
         on = lambda x: torch.as_tensor(x, dtype=torch.float32).to(dev)     # noqa: E731
         return projection(vertices, on(K), on(R), on(t), on(dist_coeffs), orig_size)
 
-    def _rasterize(self, vertices, faces, textures, cam, return_index=False):
+    def _prepare_faces(self, vertices, faces, textures, cam, face_opacity=None, projected=None):
+        """what the rasteriser needs of a mesh: projected triangles, textures, light (None without textures), opacity -- with
+        both windings when fill_back is set (renderer.py:119-152).  projected (B,V,3): the vertices under a camera of the
+        caller's instead of this renderer's (the light always sees the world vertices)"""
         vertices = vertices.detach().float()
         faces = faces.detach()
         light = None
@@ -276,11 +358,17 @@ class Renderer(nn.Module):
         if self.fill_back:
             faces = torch.cat((faces, faces.flip(-1)), dim=1)
             textures = torch.cat((textures, textures.permute((0, 1, 4, 3, 2, 5))), dim=1)
+            if face_opacity is not None:
+                face_opacity = torch.cat((face_opacity, face_opacity), dim=1)
         if lit:
             light = face_light(vertices_to_faces(vertices, faces), self.light_intensity_ambient,
                                self.light_intensity_directional, self.light_color_ambient, self.light_color_directional,
                                self.light_direction)
-        tri = vertices_to_faces(self.transform(vertices, *cam), faces)
+        tri = vertices_to_faces(self.transform(vertices, *cam) if projected is None else projected, faces)
+        return tri, textures, light, face_opacity
+
+    def _rasterize(self, vertices, faces, textures, cam, return_index=False):
+        tri, textures, light, _ = self._prepare_faces(vertices, faces, textures, cam)
         return rasterize_rgbad(tri, textures, light, self.image_size, self.anti_aliasing, self.near, self.far,
                                self.rasterizer_eps, self.background_color, return_index=return_index)
 
@@ -314,14 +402,34 @@ class Renderer(nn.Module):
         """world points (B,N,3) as shaded discs -> (rgb (B,3,S,S), depth (B,S,S), alpha (B,S,S)); inputs are detached.
         radius: output pixels, a number or (B,N).  world_radius (metres, a number or (B,N)) replaces it by the per-point
         pixel radius focal_px * world_radius / z."""
-        points = points.detach().float()
-        ndc = self.transform(points, K, R, t, dist_coeffs, orig_size)
+        ndc, radius = self._prepare_points(points, radius, world_radius, (K, R, t, dist_coeffs, orig_size))
+        out = splat_points(ndc, colors, radius, self.image_size, self.anti_aliasing, self.near, self.far,
+                           background_color=self.background_color)
+        return out["rgb"], out["depth"], out["alpha"]
+
+    def _prepare_points(self, points, radius, world_radius, cam):
+        """projected points and their radius in output pixels (`radius`, or focal_px * world_radius / z)"""
+        K, orig_size = cam[0], cam[4]
+        ndc = self.transform(points.detach().float(), *cam)
         if world_radius is not None:
             focal = self.focal_pixels(K, orig_size)
             if torch.is_tensor(focal):
                 focal = focal.to(ndc.device).view(-1, 1)
             wr = torch.as_tensor(world_radius, dtype=torch.float32).to(ndc.device)
             radius = world_radius_to_pixels(wr, ndc[:, :, 2], focal).expand(ndc.shape[0], ndc.shape[1])
-        out = splat_points(ndc, colors, radius, self.image_size, self.anti_aliasing, self.near, self.far,
-                           background_color=self.background_color)
+        return ndc, radius
+
+    def render_scene(self, vertices, faces, textures, points, colors=None, radius=2.0, world_radius=None, face_opacity=None,
+                     point_depth_bias=0.0, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
+        """a mesh (as `render` takes it) and world points (as `render_points` takes them) in one image, occluding each other
+        per sample -> (rgb (B,3,S,S), depth (B,S,S), alpha (B,S,S)); inputs are detached.  face_opacity (B,F) or None =
+        opaque, per face of `faces` (both windings get it under fill_back); point_depth_bias: see `rasterize_scene`."""
+        cam = (K, R, t, dist_coeffs, orig_size)
+        if face_opacity is not None:
+            face_opacity = torch.as_tensor(face_opacity, dtype=torch.float32).to(vertices.device)
+        tri, textures, light, face_opacity = self._prepare_faces(vertices, faces, textures, cam, face_opacity)
+        ndc, radius = self._prepare_points(points.to(vertices.device), radius, world_radius, cam)
+        out = rasterize_scene(tri, textures, light, ndc, colors, radius, face_opacity, point_depth_bias, self.image_size,
+                              self.anti_aliasing, self.near, self.far, self.rasterizer_eps,
+                              background_color=self.background_color)
         return out["rgb"], out["depth"], out["alpha"]

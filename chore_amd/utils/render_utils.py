@@ -76,6 +76,28 @@ def load_mesh(pcfile):
     return Mesh(filename=pcfile) if os.path.isfile(pcfile) else None
 
 
+def icosphere_mesh(center, radius, subdiv=2):
+    """a sphere as a `Mesh`: the icosahedron with every triangle split in four `subdiv` times and the new vertices pushed out
+    to the sphere (20 * 4**subdiv faces, wound so that the normals point outwards).  The centre markers of the debug views."""
+    g = (1.0 + 5.0 ** 0.5) / 2.0
+    # twelve vertices on three golden rectangles; five faces round vertex 0, the five next to them, and the same below
+    v = np.array([(-1, g, 0), (1, g, 0), (-1, -g, 0), (1, -g, 0), (0, -1, g), (0, 1, g), (0, -1, -g), (0, 1, -g),
+                  (g, 0, -1), (g, 0, 1), (-g, 0, -1), (-g, 0, 1)], dtype=np.float64)
+    f = np.array([(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6),
+                  (7, 1, 8), (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10),
+                  (8, 6, 7), (9, 8, 1)], dtype=np.int64)
+    v /= np.linalg.norm(v, axis=1, keepdims=True)
+    for _ in range(int(subdiv)):
+        edges = np.sort(np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]]), axis=1)       # (3F,2): ab, bc, ca of every face
+        uniq, inv = np.unique(edges, axis=0, return_inverse=True)
+        mid = v[uniq[:, 0]] + v[uniq[:, 1]]
+        ab, bc, ca = (len(v) + inv.reshape(-1)).reshape(3, len(f))
+        v = np.concatenate([v, mid / np.linalg.norm(mid, axis=1, keepdims=True)])
+        a, b, c = f.T
+        f = np.concatenate([np.stack(t, 1) for t in ((a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca))])
+    return Mesh(v=v * float(radius) + np.asarray(center, dtype=np.float64).reshape(1, 3), f=f)
+
+
 def cal_norm_scale(meshes, maxd=2.0):
     """the factor that brings the longest edge of the meshes' common bounding box to `maxd`"""
     pts = np.concatenate([np.asarray(m.v) for m in meshes], axis=0)
@@ -158,12 +180,7 @@ class NrWrapper:
 
     def prepare_render(self, meshes, colors=None):
         """-> vertices (1, sum V, 3) float32, faces (1, sum F, 3) int32, textures (1, sum F, 4, 4, 4, 3) on self.device"""
-        palette = self.colors if colors is None else colors
-        pairs = list(zip(meshes, palette))
-        verts = [torch.as_tensor(np.asarray(m.v), dtype=torch.float32).to(self.device)[None] for m, _ in pairs]
-        faces = [torch.as_tensor(np.asarray(m.f).astype(np.int32)).to(self.device) for m, _ in pairs]
-        all_faces, textures = get_faces_and_textures(verts, faces, colors_list=[c for _, c in pairs])
-        return torch.cat(verts, dim=1), all_faces, textures
+        return mesh_tensors(meshes, self.colors if colors is None else colors, self.device)
 
     def render_points(self, renderer, clouds, colors, world_radius):
         """several point clouds in ONE splat call, so that occlusion between them is resolved per sample and nothing has to
@@ -171,6 +188,19 @@ class NrWrapper:
         number for all or one per cloud.  -> image (S,S,3) float in [0,1], coverage (S,S) float in [0,1]"""
         pts, col, rad = concat_clouds(clouds, colors, world_radius, self.device)
         rgb, _, alpha = renderer.render_points(pts[None], col[None], world_radius=rad[None])
+        return rgb[0].permute(1, 2, 0).clamp(0, 1).cpu().numpy(), alpha[0].cpu().numpy()
+
+    def render_scene(self, renderer, meshes, clouds, colors, world_radius, mesh_colors=None, mesh_opacity=1.0,
+                     point_depth_bias=0.0):
+        """meshes and point clouds in ONE scene call, occluding each other per sample: meshes / mesh_colors as `render_meshes`
+        takes them, mesh_opacity one number for all or one per mesh, clouds / colors / world_radius as `render_points` does,
+        point_depth_bias in metres (Renderer.render_scene).  -> image (S,S,3) float in [0,1], coverage (S,S) float in [0,1]"""
+        verts, faces, textures = self.prepare_render(meshes, mesh_colors)
+        pts, col, rad = concat_clouds(clouds, colors, world_radius, self.device)
+        rgb, _, alpha = renderer.render_scene(verts, faces, textures, pts[None], col[None], world_radius=rad[None],
+                                              face_opacity=mesh_face_opacity(meshes, mesh_opacity, self.device,
+                                                                             self.colors if mesh_colors is None else mesh_colors),
+                                              point_depth_bias=point_depth_bias)
         return rgb[0].permute(1, 2, 0).clamp(0, 1).cpu().numpy(), alpha[0].cpu().numpy()
 
     def prepare_side_rend(self, meshes, maxd=1.5, colors=None):
@@ -203,6 +233,27 @@ class NrWrapper:
         return twin
 
 
+def mesh_tensors(meshes, colors, device):
+    """meshes with .v / .f and one colour each -> vertices (1, sum V, 3) float32, faces (1, sum F, 3) int32, uniform textures
+    (1, sum F, 4, 4, 4, 3) on `device`; a mesh without a colour is left out (zip)"""
+    pairs = list(zip(meshes, colors))
+    verts = [torch.as_tensor(np.asarray(m.v), dtype=torch.float32).to(device)[None] for m, _ in pairs]
+    faces = [torch.as_tensor(np.asarray(m.f).astype(np.int32)).to(device) for m, _ in pairs]
+    all_faces, textures = get_faces_and_textures(verts, faces, colors_list=[c for _, c in pairs])
+    return torch.cat(verts, dim=1), all_faces, textures
+
+
+def mesh_face_opacity(meshes, mesh_opacity, device, colors=None):
+    """one number for all meshes or one per mesh -> (1, sum F) float32, in the face order of `mesh_tensors`.  With `colors`
+    (what `mesh_tensors` gets) a mesh without a colour is an error here, since `mesh_tensors` would leave it out"""
+    if not isinstance(mesh_opacity, (list, tuple)):
+        mesh_opacity = [mesh_opacity] * len(meshes)
+    if len(mesh_opacity) != len(meshes) or (colors is not None and len(colors) < len(meshes)):
+        raise ValueError("%d meshes need %d opacities (got %d) and as many colours (got %s)"
+                         % (len(meshes), len(meshes), len(mesh_opacity), "none" if colors is None else len(colors)))
+    return torch.cat([torch.full((len(m.f),), float(o), device=device) for m, o in zip(meshes, mesh_opacity)])[None]
+
+
 def concat_clouds(clouds, colors, radii, device):
     """clouds [(N_i,3)], colors [(3,) or (N_i,3)], radii a number or one per cloud -> points (N,3), colours (N,3), radii (N,)
     float32 tensors on `device`, cloud after cloud (tensors already there are not copied through the host)"""
@@ -217,6 +268,58 @@ def concat_clouds(clouds, colors, radii, device):
         col.append(c.reshape(1, 3).expand(len(p), 3) if c.numel() == 3 else c.reshape(len(p), 3))
         rad.append(torch.full((len(p),), float(r), device=device))
     return torch.cat(pts), torch.cat(col), torch.cat(rad)
+
+
+def _input_view_ndc(camera, pts, crop_center_b):
+    """camera-space points (N,3) through the network's camera -> (1,N,3) [u, v, z]: `camera.project_points` gives
+    [nx, ny, z] and the rasterisers take v = -ny, since their output rows are flipped"""
+    proj = camera.project_points(pts[None], crop_center_b.to(pts.device).float().reshape(1, 2)).transpose(1, 2)     # (1,N,3)
+    return torch.stack([proj[..., 0], -proj[..., 1], proj[..., 2]], dim=-1)
+
+
+def _append_markers(ndc, col, rad_px, markers2d, S, near):
+    """the 2-D markers as splats at a depth just inside `near`, so they win every sample they cover"""
+    dev = ndc.device
+    for xy, c, r in markers2d or ():
+        xy = torch.as_tensor(np.asarray(xy.detach().cpu()) if torch.is_tensor(xy) else np.asarray(xy), dtype=torch.float32)
+        xy = xy.reshape(-1, 2).to(dev)
+        u, v = (2 * xy[:, 0] + 1) / S - 1, -((2 * xy[:, 1] + 1) / S - 1)
+        ndc = torch.cat([ndc, torch.stack([u, v, torch.full_like(u, near * 1.01)], -1)[None]], 1)
+        col = torch.cat([col, torch.tensor(c, dtype=torch.float32, device=dev).reshape(1, 3).expand(len(xy), 3)])
+        rad_px = torch.cat([rad_px, torch.full((1, len(xy)), float(r), device=dev)], 1)
+    return ndc, col, rad_px
+
+
+def _over_photo(out, images_b, S):
+    """a rasteriser's rgb / alpha over the frame's photo -> (S,S,3) uint8.  The colours are weighted by their coverage already"""
+    dev = images_b.device
+    photo = images_b[:3].detach().float().clamp(0, 1)
+    if photo.shape[1] != S or photo.shape[2] != S:         # nearest-neighbour to the view's size
+        iy = (torch.arange(S, device=dev) * photo.shape[1]) // S
+        ix = (torch.arange(S, device=dev) * photo.shape[2]) // S
+        photo = photo[:, iy][:, :, ix]
+    front = out["rgb"][0] + (1 - out["alpha"][0])[None] * photo
+    return (front.permute(1, 2, 0).clamp(0, 1) * 255).to(torch.uint8).cpu().numpy()
+
+
+def _side_normalisation(pts, maxd):
+    """prepare_side_rend on the device: y flipped, the bounding box of the finite points scaled to `maxd` (cal_norm_scale),
+    centred at their mean -> (scale, place) with place(x) = scale * (x * _FLIP_Y - mean)"""
+    flip = torch.tensor(_FLIP_Y, dtype=torch.float32, device=pts.device)
+    flipped = pts * flip
+    keep = torch.isfinite(flipped).all(dim=1, keepdim=True)
+    big = torch.finfo(torch.float32).max
+    extent = torch.where(keep, flipped, -big).amax(0) - torch.where(keep, flipped, big).amin(0)
+    scale = (maxd / extent.clamp(min=1e-12)).min()
+    mean = torch.where(keep, flipped, 0.0).sum(0) / keep.sum().clamp(min=1)
+    return scale, lambda x: scale * (x * flip - mean)
+
+
+def _side_crop(rgb, S):
+    """the middle S rows of a rendering (1,3,H,W) -> (S,W,3) uint8"""
+    side = (rgb[0].permute(1, 2, 0).clamp(0, 1) * 255).to(torch.uint8).cpu().numpy()
+    top = (side.shape[0] - S) // 2
+    return side[top:top + S]
 
 
 def render_cloud_views(images_b, crop_center_b, clouds, colors, radii, markers2d=None, side_renderer=None, camera=None,
@@ -236,45 +339,63 @@ def render_cloud_views(images_b, crop_center_b, clouds, colors, radii, markers2d
     camera = KinectColorCamera() if camera is None else camera
     pts, col, rad = concat_clouds(clouds, colors, radii, dev)
     S, near = CLOUD_VIEW_SIZE, nr.renderer.DEFAULT_NEAR
-    proj = camera.project_points(pts[None], crop_center_b.to(dev).float().reshape(1, 2)).transpose(1, 2)     # (1,N,3)
-    ndc = torch.stack([proj[..., 0], -proj[..., 1], proj[..., 2]], dim=-1)
+    ndc = _input_view_ndc(camera, pts, crop_center_b)
     focal = camera.fx_px * S / camera.crop_size
     rad_px = nr.world_radius_to_pixels(rad[None], ndc[..., 2], focal).clamp(min=min_radius_px)
-    if markers2d:
-        for xy, c, r in markers2d:
-            xy = torch.as_tensor(np.asarray(xy.detach().cpu()) if torch.is_tensor(xy) else np.asarray(xy), dtype=torch.float32)
-            xy = xy.reshape(-1, 2).to(dev)
-            u, v = (2 * xy[:, 0] + 1) / S - 1, -((2 * xy[:, 1] + 1) / S - 1)
-            ndc = torch.cat([ndc, torch.stack([u, v, torch.full_like(u, near * 1.01)], -1)[None]], 1)
-            col = torch.cat([col, torch.tensor(c, dtype=torch.float32, device=dev).reshape(1, 3).expand(len(xy), 3)])
-            rad_px = torch.cat([rad_px, torch.full((1, len(xy)), float(r), device=dev)], 1)
+    n = len(pts)
+    ndc, col, rad_px = _append_markers(ndc, col, rad_px, markers2d, S, near)
     out = nr.splat_points(ndc, col[None], rad_px, S, True, near, nr.renderer.DEFAULT_FAR, ambient=0.6)
-    photo = images_b[:3].detach().float().clamp(0, 1)
-    if photo.shape[1] != S or photo.shape[2] != S:         # nearest-neighbour to the view's size
-        iy = (torch.arange(S, device=dev) * photo.shape[1]) // S
-        ix = (torch.arange(S, device=dev) * photo.shape[2]) // S
-        photo = photo[:, iy][:, :, ix]
-    front = out["rgb"][0] + (1 - out["alpha"][0])[None] * photo        # the splat colours are weighted by their coverage already
-    front = (front.permute(1, 2, 0).clamp(0, 1) * 255).to(torch.uint8).cpu().numpy()
+    front = _over_photo(out, images_b, S)
 
     side_renderer = setup_side_renderer(2.0, 0., 90.) if side_renderer is None else side_renderer
-    n = len(pts)
-    # prepare_side_rend on the device: y flipped, the bounding box scaled to `maxd` (cal_norm_scale), centred at the mean
-    flipped = pts * torch.tensor(_FLIP_Y, dtype=torch.float32, device=dev)
-    keep = torch.isfinite(flipped).all(dim=1, keepdim=True)
-    big = torch.finfo(torch.float32).max
-    extent = torch.where(keep, flipped, -big).amax(0) - torch.where(keep, flipped, big).amin(0)
-    scale = (maxd / extent.clamp(min=1e-12)).min()
-    mean = torch.where(keep, flipped, 0.0).sum(0) / keep.sum().clamp(min=1)
-    centred = scale * (flipped - mean)
-    side_ndc = side_renderer.transform(centred[None])
+    scale, place = _side_normalisation(pts, maxd)
+    side_ndc = side_renderer.transform(place(pts)[None])
     side_px = nr.world_radius_to_pixels((rad * scale)[None], side_ndc[..., 2], side_renderer.focal_pixels())
     rgb = nr.splat_points(side_ndc, col[None, :n], side_px.clamp(min=min_radius_px), side_renderer.image_size,
                           side_renderer.anti_aliasing, side_renderer.near, side_renderer.far,
                           background_color=side_renderer.background_color)["rgb"]
-    side = (rgb[0].permute(1, 2, 0).clamp(0, 1) * 255).to(torch.uint8).cpu().numpy()
-    top = (side.shape[0] - S) // 2
-    return np.concatenate([front, side[top:top + S]], axis=1)
+    return np.concatenate([front, _side_crop(rgb, S)], axis=1)
+
+
+def render_scene_views(images_b, crop_center_b, meshes, mesh_colors, mesh_opacity, clouds, colors, radii, markers2d=None,
+                       point_depth_bias=0.0, side_renderer=None, camera=None, maxd=1.5, min_radius_px=1.0):
+    """meshes AND point clouds of ONE frame in the two views of `render_cloud_views` -> (512, 512 + 640, 3) uint8, each view one
+    scene call (chore_scene_fwd), so meshes and points occlude each other per sample.
+
+    meshes with .v (camera space) / .f, mesh_colors one colour each, mesh_opacity one number for all or one per mesh (a
+    translucent face shows the nearest point behind it or the background, never another face); point_depth_bias in metres
+    (scaled with the side view); the rest as `render_cloud_views` takes it.  The meshes go through exactly the clouds'
+    transforms: the network's camera with v = -ny in the input view (lit like setup_renderer's front view), and in the side
+    view the y-flip, scale and centring, which are computed from the cloud points and the mesh vertices together."""
+    if not meshes:
+        raise ValueError("render_scene_views needs at least one mesh; render_cloud_views draws clouds alone")
+    dev = images_b.device
+    camera = KinectColorCamera() if camera is None else camera
+    pts, col, rad = concat_clouds(clouds, colors, radii, dev)
+    verts, faces, textures = mesh_tensors(meshes, mesh_colors, dev)
+    opacity = mesh_face_opacity(meshes, mesh_opacity, dev, mesh_colors)
+    S, near, far = CLOUD_VIEW_SIZE, nr.renderer.DEFAULT_NEAR, nr.renderer.DEFAULT_FAR
+    ndc = _input_view_ndc(camera, pts, crop_center_b)
+    focal = camera.fx_px * S / camera.crop_size
+    rad_px = nr.world_radius_to_pixels(rad[None], ndc[..., 2], focal).clamp(min=min_radius_px)
+    n = len(pts)
+    ndc, col, rad_px = _append_markers(ndc, col, rad_px, markers2d, S, near)
+    front_light = _soft_light(nr.Renderer(camera_mode='look_at', image_size=S), 0.4, [1, 0.5, 1])      # carries the light only
+    tri, tex, light, op = front_light._prepare_faces(verts, faces, textures, (), opacity,
+                                                     projected=_input_view_ndc(camera, verts[0], crop_center_b))
+    out = nr.rasterize_scene(tri, tex, light, ndc, col[None], rad_px, op, point_depth_bias, S, True, near, far, ambient=0.6)
+    front = _over_photo(out, images_b, S)
+
+    side_renderer = setup_side_renderer(2.0, 0., 90.) if side_renderer is None else side_renderer
+    scale, place = _side_normalisation(torch.cat([pts, verts[0]]), maxd)
+    side_ndc = side_renderer.transform(place(pts)[None])
+    side_px = nr.world_radius_to_pixels((rad * scale)[None], side_ndc[..., 2], side_renderer.focal_pixels())
+    tri, tex, light, op = side_renderer._prepare_faces(place(verts[0])[None], faces, textures, (None,) * 5, opacity)
+    rgb = nr.rasterize_scene(tri, tex, light, side_ndc, col[None, :n], side_px.clamp(min=min_radius_px), op,
+                             float(point_depth_bias * scale), side_renderer.image_size, side_renderer.anti_aliasing,
+                             side_renderer.near, side_renderer.far, side_renderer.rasterizer_eps,
+                             background_color=side_renderer.background_color)["rgb"]
+    return np.concatenate([front, _side_crop(rgb, S)], axis=1)
 
 
 def _resize_u8(img, dsize, device):

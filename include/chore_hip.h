@@ -363,6 +363,44 @@ int chore_splat_fwd(chore_handle* h, const float* pts, const float* rgb_in, cons
                     float* depth, float* alpha, int* sample_point_index, void* workspace, chore_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Meshes and point clouds in one image, forward only  (what the reference's -d viewer shows in one view,
+ * recon/recon_fit_base.py:442-511, 749-795: point clouds next to sphere and ground-truth MESHES; the rule is this library's own).
+ * The triangle arguments (tri, textures, light, B, F, ts, tex_eps) are chore_render_fwd's, the point arguments (pts,
+ * point_rgb, radius, radius_px, N, ambient) chore_splat_fwd's; size, ssaa, near_z, far_z, background3 (HOST) serve both.
+ * face_opacity (B,F) or NULL = 1; point_depth_bias: a host scalar >= 0 in depth units.  F, N >= 1.
+ * Per sample of the size * ssaa grid, all arithmetic fp32, each operation rounded once, in the association written here:
+ *   - the face layer is exactly chore_render_fwd's: the winning face f (smallest zp, then smallest index, under the hit rule
+ *     of chore_silhouette_fwd), its colour m = texture blend times light, its depth zf = zp;
+ *   - the point layer is exactly chore_splat_fwd's: the winning point n (smallest z, then smallest index, by the 64-bit
+ *     integer atomicMin key), its shaded colour p, its depth zn;
+ *   - the point is in front iff a point covers the sample and (no face covers it, or zn - point_depth_bias < zf); equality
+ *     goes to the face.  The bias exists because fitted clouds lie ON the fitted surface: without it about half of their
+ *     points lose to their own mesh;
+ *   - o = fminf(fmaxf(face_opacity[b,f], 0), 1), NaN -> 0: clamped on the device, the host reads no device value;
+ *   - point in front: colour p, depth zn, alpha 1, sample_id = -2 - n;
+ *   - face in front: under = p where a point covers the sample (necessarily behind), otherwise background3; colour = m
+ *     untouched when o >= 1, otherwise o * m + (1 - o) * under (two products, one sum); depth zf; alpha 1 where a point
+ *     covers the sample, otherwise o; sample_id = f;
+ *   - nothing covers the sample: background3 / far_z / 0, sample_id = -1.
+ * Two layers only: a translucent face shows the nearest point behind it or the background, never another face.
+ * Outputs are resolved as chore_render_fwd's and chore_splat_fwd's: per output pixel the samples are summed in the order
+ * s = sy * ssaa + sx starting from 0 and multiplied by 1 / ssaa^2, for rgb (B,3,size,size), depth (B,size,size) and alpha
+ * (B,size,size) alike; row r holds the sample rows of block size-1-r.  sample_id (B,size*ssaa,size*ssaa) int32 or NULL, rows
+ * NOT flipped.  With no point in view the outputs equal chore_render_fwd's bit for bit, with no face chore_splat_fwd's.
+ * workspace: chore_scene_workspace_bytes(B, F, N, size, ssaa) bytes, 256-byte aligned: the render workspace, padded to 256
+ * bytes, then the keys (0 = a shape either of the two refuses).  It depends on the shapes only; every launch goes on
+ * `stream`, nothing is allocated and no device value is read by the host, so the call can be captured into a graph.
+ * CHORE_EINVAL, before anything is launched: whatever chore_render_fwd or chore_splat_fwd refuses, F < 1, N < 1,
+ * point_depth_bias negative or NaN.
+ * ------------------------------------------------------------------------------------------- */
+size_t chore_scene_workspace_bytes(int B, int F, int N, int size, int ssaa);
+int chore_scene_fwd(chore_handle* h,
+    const float* tri, const float* textures, const float* light, const float* face_opacity, int B, int F, int ts,
+    const float* pts, const float* point_rgb, const float* radius, float radius_px, int N, float point_depth_bias,
+    int size, int ssaa, float ambient, float near_z, float far_z, float tex_eps, const float* background3,
+    float* rgb, float* depth, float* alpha, int* sample_id, void* workspace, chore_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Evaluation metrics, fp64  (replace recon/eval/chamfer_distance.py:10-52 = sklearn kd-tree nearest neighbours, and
  * recon/eval/pose_utils.py compute_transform :145-180 / compute_similarity_transform :103-143).
  *   chore_eval_chamfer   out[0] = mean_i min_j |x_i - y_j| (direction 'x_to_y'), out[1] = the other direction
