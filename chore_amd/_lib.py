@@ -201,6 +201,8 @@ SIGNATURES = {
     "chore_silhouette_bwd": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     "chore_render_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "chore_render_fwd": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_float] * 3 + [c_void_p] * 7),
+    "chore_render_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "chore_render_bwd": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_float] * 4 + [c_void_p] * 9),
     "chore_splat_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "chore_splat_fwd": (c_int, [c_void_p] * 4 + [c_float] + [c_int] * 4 + [c_float] * 3 + [c_void_p] * 7),
     "chore_scene_workspace_bytes": (c_size_t, [c_int] * 5),

@@ -1,8 +1,9 @@
-// raster_common.h -- what the silhouette rasteriser (silhouette.hip) and the colour / depth rasteriser (render.hip) share:
-// the per-triangle setup and the per-sample hit rule of neural_renderer's forward_face_index_map
-// (external/neural_renderer/neural_renderer/cuda/rasterize_cuda_kernel.cu:24-215).  Both kernels evaluate these very
-// expressions (explicit __fmul_rn, fixed association, -ffp-contract=off), so the face that wins a sample is the same bit
-// for bit in both.
+// raster_common.h -- what the silhouette rasteriser (silhouette.hip) and the colour / depth rasteriser (render.hip,
+// render_bwd.hip) share: the per-triangle setup and the per-sample hit rule of neural_renderer's forward_face_index_map
+// (external/neural_renderer/neural_renderer/cuda/rasterize_cuda_kernel.cu:24-215), and the edge walk of its
+// backward_pixel_map (:290-549).  All kernels evaluate these very expressions (explicit __fmul_rn, fixed association,
+// -ffp-contract=off), so the face that wins a sample is the same bit for bit in them, and so is the alpha term of the
+// pixel-map gradient.
 #pragma once
 #include "common.h"
 
@@ -52,14 +53,9 @@ __device__ __forceinline__ void tri_setup(TriSetup& t, int size) {
 // normalised coordinate of the centre of pixel i of `size` (evaluated in double, stored as float, like the reference)
 __device__ __forceinline__ float raster_centre(int i, int size) { return (float)((2.0 * i + 1 - size) / size); }
 
-// does the sample (xp, yp) normalised / (xf, yf) pixel hit the front-facing triangle (f, inverse m)?  On a hit: the clamped
-// and renormalised barycentric weights and the perspective-correct depth zp, already checked against near / far.
-__device__ __forceinline__ bool raster_hit(const float* f, const float* m, float xp, float yp, float xf, float yf, float near,
-                                           float far, float* w, float& zp) {
-    if (__fmul_rn(yp - f[1], f[3] - f[0]) < __fmul_rn(xp - f[0], f[4] - f[1]) ||
-        __fmul_rn(yp - f[4], f[6] - f[3]) < __fmul_rn(xp - f[3], f[7] - f[4]) ||
-        __fmul_rn(yp - f[7], f[0] - f[6]) < __fmul_rn(xp - f[6], f[1] - f[7]))
-        return false;
+// the clamped and renormalised barycentric weights of the pixel (xf, yf) under the pixel-space inverse m, and the
+// perspective-correct depth zp they give on the triangle f: what a hit keeps, and what the backward rebuilds for a winner
+__device__ __forceinline__ void raster_weights(const float* f, const float* m, float xf, float yf, float* w, float& zp) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         float v = (m[3 * k] * xf + m[3 * k + 1] * yf) + m[3 * k + 2];
@@ -70,7 +66,140 @@ __device__ __forceinline__ bool raster_hit(const float* f, const float* m, float
 #pragma unroll
     for (int k = 0; k < 3; ++k) w[k] = w[k] / ws;
     zp = 1.0f / ((w[0] / f[2] + w[1] / f[5]) + w[2] / f[8]);
+}
+
+// does the sample (xp, yp) normalised / (xf, yf) pixel hit the front-facing triangle (f, inverse m)?  On a hit: the clamped
+// and renormalised barycentric weights and the perspective-correct depth zp, already checked against near / far.
+__device__ __forceinline__ bool raster_hit(const float* f, const float* m, float xp, float yp, float xf, float yf, float near,
+                                           float far, float* w, float& zp) {
+    if (__fmul_rn(yp - f[1], f[3] - f[0]) < __fmul_rn(xp - f[0], f[4] - f[1]) ||
+        __fmul_rn(yp - f[4], f[6] - f[3]) < __fmul_rn(xp - f[3], f[7] - f[4]) ||
+        __fmul_rn(yp - f[7], f[0] - f[6]) < __fmul_rn(xp - f[6], f[1] - f[7]))
+        return false;
+    raster_weights(f, m, xf, yf, w, zp);
     return !(zp <= near || far <= zp);
+}
+
+// ---- the backward of the pixel map (rasterize_cuda_kernel.cu:290-549): the edge walk, shared by silhouette.hip (alpha
+// alone) and render_bwd.hip (alpha + rgb).  An image type Im says what a pixel holds and what it contributes:
+//   int size;  size_t at(axis, d0, d1): the pixel with coordinate d0 along the walk axis and d1 across it;
+//   int face(q): its winning face;  Ref ref(q): its values as the 'in' / 'out' pixel of a crossing;
+//   Px load(q): its values and upstream gradients;  float diff(px, ref): diff_grad, summed over the channels BEFORE the gate.
+constexpr int EDGE_U = 8;     // pixels of a line whose loads are in flight together
+// One walk along edge (P0 -> P1) of triangle fn on one axis; P2 is the opposite vertex.  u = coordinate along the walk
+// axis, v = across it.  Adds to g0 / g1 (the gradient of P0 / P1 along v).  The 64 lanes of a wave share one walk: lane l
+// takes the positions d0_from + l, + 64, ... along the edge.
+template <class Im>
+__device__ void raster_edge_walk(const Im& im, int fn, int axis, float u0, float v0, float u1, float v1, float u2, float v2,
+                                 float eps, int lane, float& g0, float& g1) {
+    const int size = im.size;
+    const float S = (float)size;
+    int direction;
+    if (axis == 0) direction = (u0 < u1) ? -1 : 1;
+    else direction = (u0 < u1) ? 1 : -1;
+    const int d0_from = (int)fmaxf(ceilf(fminf(u0, u1)), 0.f);
+    const int d0_to = (int)fminf(fmaxf(u0, u1), S - 1.f);
+    for (int d0 = d0_from + lane; d0 <= d0_to; d0 += 64) {
+        const float fd0 = (float)d0;
+        const float cross = (v1 - v0) / (u1 - u0) * (fd0 - u0) + v0;
+        if (!(fabsf(cross) <= 3.0e38f)) continue;          // non-finite: degenerate edge
+        const int d1_in = direction > 0 ? (int)floorf(cross) : (int)ceilf(cross);
+        const int d1_out = d1_in + direction;
+        if (d1_in < 0 || d1_in >= size || d1_out < 0 || d1_out >= size) continue;
+        const typename Im::Ref r_in = im.ref(im.at(axis, d0, d1_in)), r_out = im.ref(im.at(axis, d0, d1_out));
+        auto push = [&](int d1, float diff) {
+            if (!(diff > 0.f)) return;
+            const float t = ((float)d1 - cross);
+            if (u1 != fd0) {
+                float dist = (u1 - u0) / (u1 - fd0) * t * 2.0f / S;
+                dist = dist > 0.f ? dist + eps : dist - eps;
+                g0 -= diff / dist;
+            }
+            if (u0 != fd0) {
+                float dist = (u1 - u0) / (fd0 - u0) * t * 2.0f / S;
+                dist = dist > 0.f ? dist + eps : dist - eps;
+                g1 -= diff / dist;
+            }
+        };
+        if (im.face(im.at(axis, d0, d1_in)) == fn) {         // 'out': beyond the edge up to the image border
+            const int lim = direction > 0 ? size - 1 : 0;
+            const int lo = max(min(d1_out, lim), 0), hi = min(max(d1_out, lim), size - 1);
+            for (int d1 = lo; d1 <= hi; d1 += EDGE_U) {     // EDGE_U pixels' loads requested together, pushed in pixel order
+                typename Im::Px px[EDGE_U];
+#pragma unroll
+                for (int u = 0; u < EDGE_U; ++u) px[u] = im.load(im.at(axis, d0, min(d1 + u, hi)));
+#pragma unroll
+                for (int u = 0; u < EDGE_U; ++u)
+                    if (d1 + u <= hi) push(d1 + u, im.diff(px[u], r_in));
+            }
+        }
+        float c2;                                            // 'in': this face's pixels up to the opposite edge
+        if ((fd0 - u0) * (fd0 - u2) < 0.f) c2 = (v2 - v0) / (u2 - u0) * (fd0 - u0) + v0;
+        else c2 = (v1 - v2) / (u1 - u2) * (fd0 - u2) + v2;
+        if (!(fabsf(c2) <= 3.0e38f)) continue;
+        const int lim = direction > 0 ? (int)ceilf(c2) : (int)floorf(c2);
+        const int lo = max(min(d1_in, lim), 0), hi = min(max(d1_in, lim), size - 1);
+        for (int d1 = lo; d1 <= hi; d1 += EDGE_U) {
+            typename Im::Px px[EDGE_U];
+            int fm[EDGE_U];
+#pragma unroll
+            for (int u = 0; u < EDGE_U; ++u) {
+                const size_t q = im.at(axis, d0, min(d1 + u, hi));
+                fm[u] = im.face(q); px[u] = im.load(q);
+            }
+#pragma unroll
+            for (int u = 0; u < EDGE_U; ++u)
+                if (d1 + u <= hi && fm[u] == fn) push(d1 + u, im.diff(px[u], r_out));
+        }
+    }
+}
+
+// The six walks of one front-facing triangle f (index fn of image im) by a workgroup of 384 threads: a wave takes one
+// (edge, axis) walk, a lane one position along the edge.  The reference gives a whole triangle to ONE thread, whose six walks
+// of up to `size` positions x up to `size` pixels each are a serial chain of tens of thousands of dependent loads.  The
+// per-lane partial sums are combined with a fixed butterfly and the six walks in the reference's order (edges 0, 1, 2, axis 0
+// before axis 1), so the result is deterministic; it differs from the serial sum by fp32 round-off only.  Every thread of
+// the workgroup must call it; thread 0 stores the nine components (depth components zero) to g9.  part: LDS.
+template <class Im>
+__device__ __forceinline__ void raster_pixel_map_bwd(const Im& im, const float* f, int fn, bool back, float eps,
+                                                     float (&part)[6][2], float* __restrict__ g9) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    float g0 = 0.f, g1 = 0.f;
+    if (!back) {
+        const float S = (float)im.size;
+        float px[3], py[3];
+#pragma unroll
+        for (int v = 0; v < 3; ++v) {
+            px[v] = 0.5f * ((f[3 * v] * S + S) - 1.0f);
+            py[v] = 0.5f * ((f[3 * v + 1] * S + S) - 1.0f);
+        }
+        const int e = wave >> 1, axis = wave & 1;
+        const int i0 = e, i1 = (e + 1) % 3, i2 = (e + 2) % 3;
+        // axis 0: walk x, the gradient goes to y; axis 1: walk y, the gradient goes to x
+        if (axis == 0) raster_edge_walk(im, fn, 0, px[i0], py[i0], px[i1], py[i1], px[i2], py[i2], eps, lane, g0, g1);
+        else raster_edge_walk(im, fn, 1, py[i0], px[i0], py[i1], px[i1], py[i2], px[i2], eps, lane, g0, g1);
+#pragma unroll
+        for (int o = 32; o; o >>= 1) {
+            g0 += __shfl_xor(g0, o);
+            g1 += __shfl_xor(g1, o);
+        }
+    }
+    if (lane == 0) { part[wave][0] = g0; part[wave][1] = g1; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float g[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) g[k] = 0.f;
+        for (int e = 0; e < 3; ++e) {
+            const int i0 = e, i1 = (e + 1) % 3;
+            g[3 * i0 + 1] += part[2 * e][0];
+            g[3 * i1 + 1] += part[2 * e][1];
+            g[3 * i0 + 0] += part[2 * e + 1][0];
+            g[3 * i1 + 0] += part[2 * e + 1][1];
+        }
+#pragma unroll
+        for (int k = 0; k < 9; ++k) g9[k] = g[k];
+    }
 }
 
 }  // namespace

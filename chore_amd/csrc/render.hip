@@ -1,4 +1,4 @@
-// render.hip -- colour / depth / coverage rasterisation of the fitted meshes (forward only, for visualisation).
+// render.hip -- colour / depth / coverage rasterisation of the fitted meshes: the forward (the backward is render_bwd.hip).
 //
 // Replaces what Renderer.render (external/neural_renderer/neural_renderer/renderer.py:237-283) gets from rasterize_rgbad
 // (rasterize.py:267-348): the CUDA kernels forward_face_index_map, forward_texture_sampling, forward_background and

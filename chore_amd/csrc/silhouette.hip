@@ -89,138 +89,35 @@ __global__ __launch_bounds__(256) void sil_fwd_kernel(const TriSetup* __restrict
     }
 }
 
-// one walk along edge (P0 -> P1) of triangle fn on one axis; P2 is the opposite vertex.  u = coordinate along the
-// walk axis, v = across it.  Adds to g0 / g1 (the gradient of P0 / P1 along v).
-struct Img {
+// what the shared edge walk (raster_common.h) sees of the silhouette image: one channel
+struct SilImg {
     const int* fim; const float* alpha; const float* grad; int size;
+    struct Ref { float a; };
+    struct Px { float al, gr; };
     __device__ __forceinline__ size_t at(int axis, int d0, int d1) const {
         return axis == 0 ? (size_t)d1 * size + d0 : (size_t)d0 * size + d1;
     }
+    __device__ __forceinline__ int face(size_t q) const { return fim[q]; }
+    __device__ __forceinline__ Ref ref(size_t q) const { return Ref{alpha[q]}; }
+    __device__ __forceinline__ Px load(size_t q) const { return Px{alpha[q], grad[q]}; }
+    __device__ __forceinline__ float diff(const Px& p, const Ref& r) const { return (p.al - r.a) * p.gr; }
 };
 
-constexpr int SIL_U = 8;     // pixels of a line whose loads are in flight together
-// The 64 lanes of a wave share one walk: lane l takes the positions d0_from + l, + 64, ... along the edge.
-__device__ void sil_edge_walk(const Img& im, int fn, int axis, float u0, float v0, float u1, float v1, float u2, float v2,
-                              float eps, int lane, float& g0, float& g1) {
-    const int size = im.size;
-    const float S = (float)size;
-    int direction;
-    if (axis == 0) direction = (u0 < u1) ? -1 : 1;
-    else direction = (u0 < u1) ? 1 : -1;
-    const int d0_from = (int)fmaxf(ceilf(fminf(u0, u1)), 0.f);
-    const int d0_to = (int)fminf(fmaxf(u0, u1), S - 1.f);
-    for (int d0 = d0_from + lane; d0 <= d0_to; d0 += 64) {
-        const float fd0 = (float)d0;
-        const float cross = (v1 - v0) / (u1 - u0) * (fd0 - u0) + v0;
-        if (!(fabsf(cross) <= 3.0e38f)) continue;          // non-finite: degenerate edge
-        const int d1_in = direction > 0 ? (int)floorf(cross) : (int)ceilf(cross);
-        const int d1_out = d1_in + direction;
-        if (d1_in < 0 || d1_in >= size || d1_out < 0 || d1_out >= size) continue;
-        const float a_in = im.alpha[im.at(axis, d0, d1_in)], a_out = im.alpha[im.at(axis, d0, d1_out)];
-        auto push = [&](int d1, float diff) {
-            if (!(diff > 0.f)) return;
-            const float t = ((float)d1 - cross);
-            if (u1 != fd0) {
-                float dist = (u1 - u0) / (u1 - fd0) * t * 2.0f / S;
-                dist = dist > 0.f ? dist + eps : dist - eps;
-                g0 -= diff / dist;
-            }
-            if (u0 != fd0) {
-                float dist = (u1 - u0) / (fd0 - u0) * t * 2.0f / S;
-                dist = dist > 0.f ? dist + eps : dist - eps;
-                g1 -= diff / dist;
-            }
-        };
-        if (im.fim[im.at(axis, d0, d1_in)] == fn) {          // 'out': beyond the edge up to the image border
-            const int lim = direction > 0 ? size - 1 : 0;
-            const int lo = max(min(d1_out, lim), 0), hi = min(max(d1_out, lim), size - 1);
-            for (int d1 = lo; d1 <= hi; d1 += SIL_U) {      // SIL_U pixels' loads requested together, pushed in pixel order
-                float al[SIL_U], gr[SIL_U];
-#pragma unroll
-                for (int u = 0; u < SIL_U; ++u) {
-                    const size_t q = im.at(axis, d0, min(d1 + u, hi));
-                    al[u] = im.alpha[q]; gr[u] = im.grad[q];
-                }
-#pragma unroll
-                for (int u = 0; u < SIL_U; ++u)
-                    if (d1 + u <= hi) push(d1 + u, (al[u] - a_in) * gr[u]);
-            }
-        }
-        float c2;                                            // 'in': this face's pixels up to the opposite edge
-        if ((fd0 - u0) * (fd0 - u2) < 0.f) c2 = (v2 - v0) / (u2 - u0) * (fd0 - u0) + v0;
-        else c2 = (v1 - v2) / (u1 - u2) * (fd0 - u2) + v2;
-        if (!(fabsf(c2) <= 3.0e38f)) continue;
-        const int lim = direction > 0 ? (int)ceilf(c2) : (int)floorf(c2);
-        const int lo = max(min(d1_in, lim), 0), hi = min(max(d1_in, lim), size - 1);
-        for (int d1 = lo; d1 <= hi; d1 += SIL_U) {
-            float al[SIL_U], gr[SIL_U];
-            int fm[SIL_U];
-#pragma unroll
-            for (int u = 0; u < SIL_U; ++u) {
-                const size_t q = im.at(axis, d0, min(d1 + u, hi));
-                fm[u] = im.fim[q]; al[u] = im.alpha[q]; gr[u] = im.grad[q];
-            }
-#pragma unroll
-            for (int u = 0; u < SIL_U; ++u)
-                if (d1 + u <= hi && fm[u] == fn) push(d1 + u, (al[u] - a_out) * gr[u]);
-        }
-    }
-}
-
-// One workgroup per triangle, one wave per walk (3 edges x 2 axes), one lane per position along the edge: the reference
-// (rasterize_cuda_kernel.cu:290-549) gives a whole triangle to ONE thread, whose six walks of up to `size` positions x up
-// to `size` pixels each are a serial chain of tens of thousands of dependent loads -- 5.4 ms for a 1 024-triangle
-// template that fills the 256-px ROI.  The per-lane partial sums are combined with a fixed butterfly and the six walks
-// in the reference's order, so the result is deterministic; it differs from the serial sum by fp32 round-off only.
+// One workgroup per triangle, one wave per walk (3 edges x 2 axes), one lane per position along the edge
+// (raster_pixel_map_bwd): 5.4 ms in the reference's one-thread-per-triangle form for a 1 024-triangle template that fills
+// the 256-px ROI.
 __global__ __launch_bounds__(384) void sil_bwd_kernel(const float* __restrict__ faces, const int* __restrict__ face_index,
                                                       const float* __restrict__ alpha, const float* __restrict__ grad_alpha,
                                                       int B, int F, int size, float eps, float* __restrict__ grad_faces) {
     const int i = blockIdx.x;
     const int b = i / F, fn = i % F;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     __shared__ float part[6][2];
     float f[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) f[k] = faces[(size_t)i * 9 + k];
-    const bool back = tri_backside(f);
-    float g0 = 0.f, g1 = 0.f;
-    if (!back) {
-        const size_t img = (size_t)b * size * size;
-        const Img im{face_index + img, alpha + img, grad_alpha + img, size};
-        const float S = (float)size;
-        float px[3], py[3];
-#pragma unroll
-        for (int v = 0; v < 3; ++v) {
-            px[v] = 0.5f * ((f[3 * v] * S + S) - 1.0f);
-            py[v] = 0.5f * ((f[3 * v + 1] * S + S) - 1.0f);
-        }
-        const int e = wave >> 1, axis = wave & 1;
-        const int i0 = e, i1 = (e + 1) % 3, i2 = (e + 2) % 3;
-        // axis 0: walk x, the gradient goes to y; axis 1: walk y, the gradient goes to x
-        if (axis == 0) sil_edge_walk(im, fn, 0, px[i0], py[i0], px[i1], py[i1], px[i2], py[i2], eps, lane, g0, g1);
-        else sil_edge_walk(im, fn, 1, py[i0], px[i0], py[i1], px[i1], py[i2], px[i2], eps, lane, g0, g1);
-#pragma unroll
-        for (int o = 32; o; o >>= 1) {
-            g0 += __shfl_xor(g0, o);
-            g1 += __shfl_xor(g1, o);
-        }
-    }
-    if (lane == 0) { part[wave][0] = g0; part[wave][1] = g1; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float g[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) g[k] = 0.f;
-        for (int e = 0; e < 3; ++e) {           // the reference's order: edges 0, 1, 2, axis 0 before axis 1
-            const int i0 = e, i1 = (e + 1) % 3;
-            g[3 * i0 + 1] += part[2 * e][0];
-            g[3 * i1 + 1] += part[2 * e][1];
-            g[3 * i0 + 0] += part[2 * e + 1][0];
-            g[3 * i1 + 0] += part[2 * e + 1][1];
-        }
-#pragma unroll
-        for (int k = 0; k < 9; ++k) grad_faces[(size_t)i * 9 + k] = g[k];
-    }
+    const size_t img = (size_t)b * size * size;
+    const SilImg im{face_index + img, alpha + img, grad_alpha + img, size};
+    raster_pixel_map_bwd(im, f, fn, tri_backside(f), eps, part, grad_faces + (size_t)i * 9);
 }
 
 // ---- placement + camera projection of the template, straight into the rasteriser's triangle list -----------------------

@@ -6,8 +6,10 @@ look_at.py, perspective.py, get_points_from_angles.py, rasterize.py:267-348 rast
 steps are vertex- and face-sized tensor expressions and run wherever their inputs live; rasterisation, texture sampling,
 the vertical flip and the 2x2 anti-aliasing average are one call into libchore_hip.so and need device tensors.
 
-Forward only: the reference renders for visualisation and never differentiates through `Renderer.render`; inputs that
-require grad are detached.
+Differentiable like the reference's: when grad mode is on and the vertices, the textures or the light require grad, the
+rasterisation goes through `_RasterizeRGBAD` (chore_render_fwd + chore_render_bwd) and `render`, `render_rgb`, `render_depth`,
+`render_silhouettes` and `rasterize_rgbad` carry gradients; otherwise the call is the plain forward.  The point and scene
+renderers (`splat_points`, `rasterize_scene`, `render_points`, `render_scene`) are forward only and detach their inputs.
 
 Kept quirks of the reference: `light_direction` is used un-normalised; face normals are
 normalize(cross(v0 - v1, v2 - v1), eps=1e-5), dividing by max(norm, eps); lighting sees the world vertices, before the camera.
@@ -60,6 +62,19 @@ def look_at(vertices, eye, at=(0, 0, 0), up=(0, 1, 0)):
     return torch.matmul(vertices - eye[:, None, :], r.transpose(1, 2))
 
 
+def look(vertices, eye, direction=(0, 1, 0), up=(0, 1, 0)):
+    """look.py:6-55: camera at `eye` looking along `direction` (each (3,) or (B,3); the reference's default `up` is [0, 1, 0])"""
+    if vertices.dim() != 3:
+        raise ValueError("vertices Tensor should have 3 dimensions")
+    B, dev = vertices.shape[0], vertices.device
+    eye, direction, up = _vec(eye, dev, B), _vec(direction, dev, B), _vec(up, dev, B)
+    z_axis = F.normalize(direction, eps=1e-5)
+    x_axis = F.normalize(torch.cross(up, z_axis, dim=1), eps=1e-5)
+    y_axis = F.normalize(torch.cross(z_axis, x_axis, dim=1), eps=1e-5)
+    r = torch.stack((x_axis, y_axis, z_axis), dim=1)
+    return torch.matmul(vertices - eye[:, None, :], r.transpose(1, 2))
+
+
 def perspective(vertices, angle=30.):
     """perspective.py:6-21"""
     if vertices.dim() != 3:
@@ -98,26 +113,52 @@ def lighting(faces, textures, intensity_ambient=0.5, intensity_directional=0.5, 
     return textures * light[:, :, None, None, None, :]
 
 
-def rasterize_rgbad(faces, textures, light=None, image_size=256, anti_aliasing=True, near=DEFAULT_NEAR, far=DEFAULT_FAR,
-                    eps=DEFAULT_EPS, background_color=(0, 0, 0), return_index=False):
-    """rasterize.py:267-348 in one call: faces (B,F,3,3) projected triangles, textures (B,F,ts,ts,ts,3), light (B,F,3) or None
-    -> dict(rgb (B,3,S,S), depth (B,S,S), alpha (B,S,S)[, face_index (B,S*ssaa,S*ssaa) int32, rows not flipped])"""
-    if not faces.is_cuda:
-        raise RuntimeError("chore_amd needs device tensors (no CPU path)")
-    dev = faces.device
+class _RasterizeRGBAD(torch.autograd.Function):
+    """chore_render_fwd / chore_render_bwd: (tri, textures, light or None) -> rgb, depth, alpha, sample_face_index.  The
+    forward is the plain call with the sample index kept; an output that receives no gradient hands NULL to the backward,
+    which then leaves its term out (render_depth: no pixel-map term, render_rgb: no alpha contribution)."""
+
+    @staticmethod
+    def forward(ctx, tri, tex, light, S, ssaa, near, far, eps, background_color):
+        tri, tex = tri.contiguous(), tex.contiguous()
+        light = light.contiguous() if light is not None else None
+        rgb, depth, alpha, fim = _render_fwd(tri, tex, light, S, ssaa, near, far, eps, background_color, True)
+        ctx.save_for_backward(tri, tex, light, fim)
+        ctx.args = (S, ssaa, near, far, eps, tuple(float(c) for c in background_color))
+        ctx.mark_non_differentiable(fim)
+        ctx.set_materialize_grads(False)          # an unused output hands None, not zeros, to the backward
+        return rgb, depth, alpha, fim
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_depth, g_alpha, _g_fim):
+        tri, tex, light, fim = ctx.saved_tensors
+        S, ssaa, near, far, eps, background = ctx.args
+        dev = tri.device
+        h = _lib.handle(dev.index or 0)
+        B, Fn, ts = tri.shape[0], tri.shape[1], tex.shape[2]
+        nbytes = _lib.lib.chore_render_bwd_workspace_bytes(B, Fn, ts, S, ssaa)
+        if nbytes == 0:
+            raise ValueError("unsupported render shape B=%d F=%d ts=%d image_size=%d ssaa=%d" % (B, Fn, ts, S, ssaa))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        up = [g.float().contiguous() if g is not None else None for g in (g_rgb, g_depth, g_alpha)]
+        g_tri = torch.empty_like(tri)
+        g_tex = torch.empty_like(tex) if ctx.needs_input_grad[1] else None
+        g_light = torch.empty_like(light) if light is not None and ctx.needs_input_grad[2] else None
+        ptr = lambda x: x.data_ptr() if x is not None else None      # noqa: E731
+        bg = (ctypes.c_float * 3)(*background)
+        _lib.check(_lib.lib.chore_render_bwd(h, tri.data_ptr(), tex.data_ptr(), ptr(light), fim.data_ptr(), B, Fn, ts, S, ssaa,
+                                             float(near), float(far), float(eps), float(eps), bg, ptr(up[0]), ptr(up[1]),
+                                             ptr(up[2]), g_tri.data_ptr(), ptr(g_tex), ptr(g_light), ws.data_ptr(),
+                                             torch.cuda.current_stream(dev).cuda_stream), h, "chore_render_bwd")
+        return g_tri, g_tex, g_light, None, None, None, None, None, None
+
+
+def _render_fwd(tri, tex, lt, S, ssaa, near, far, eps, background_color, return_index):
+    """one chore_render_fwd call on contiguous fp32 device tensors -> rgb, depth, alpha, sample index or None"""
+    dev = tri.device
     h = _lib.handle(dev.index or 0)
-    tri = faces.detach().float().contiguous()
-    tex = textures.detach().to(dev).float().contiguous()
     B, Fn = tri.shape[:2]
     ts = tex.shape[2]
-    if tuple(tri.shape) != (B, Fn, 3, 3) or tuple(tex.shape) != (B, Fn, ts, ts, ts, 3):
-        raise ValueError("faces (B,F,3,3) and textures (B,F,ts,ts,ts,3) expected, got %s and %s" % (tuple(tri.shape), tuple(tex.shape)))
-    lt = None
-    if light is not None:
-        lt = light.detach().to(dev).float().contiguous()
-        if tuple(lt.shape) != (B, Fn, 3):
-            raise ValueError("light (B,F,3) expected")
-    ssaa, S = (2 if anti_aliasing else 1), int(image_size)
     nbytes = _lib.lib.chore_render_workspace_bytes(B, Fn, S, ssaa)
     if nbytes == 0:
         raise ValueError("unsupported render shape B=%d F=%d image_size=%d ssaa=%d" % (B, Fn, S, ssaa))
@@ -131,6 +172,38 @@ def rasterize_rgbad(faces, textures, light=None, image_size=256, anti_aliasing=T
                                          S, ssaa, float(near), float(far), float(eps), bg, rgb.data_ptr(), depth.data_ptr(),
                                          alpha.data_ptr(), fim.data_ptr() if return_index else None, ws.data_ptr(),
                                          torch.cuda.current_stream(dev).cuda_stream), h, "chore_render_fwd")
+    return rgb, depth, alpha, fim
+
+
+def rasterize_rgbad(faces, textures, light=None, image_size=256, anti_aliasing=True, near=DEFAULT_NEAR, far=DEFAULT_FAR,
+                    eps=DEFAULT_EPS, background_color=(0, 0, 0), return_index=False):
+    """rasterize.py:267-348 in one call: faces (B,F,3,3) projected triangles, textures (B,F,ts,ts,ts,3), light (B,F,3) or None
+    -> dict(rgb (B,3,S,S), depth (B,S,S), alpha (B,S,S)[, face_index (B,S*ssaa,S*ssaa) int32, rows not flipped]).
+    Differentiable with respect to faces, textures and light when one of them requires grad and grad mode is on; `eps` is
+    the reference's one eps: the clamp of the texture sampling and the distance offset of the pixel-map gradient."""
+    if not faces.is_cuda:
+        raise RuntimeError("chore_amd needs device tensors (no CPU path)")
+    dev = faces.device
+    need_grad = torch.is_grad_enabled() and any(x is not None and x.requires_grad for x in (faces, textures, light))
+    keep = (lambda x: x) if need_grad else (lambda x: x.detach())
+    tri = keep(faces).float().contiguous()
+    tex = keep(textures).to(dev).float().contiguous()
+    B, Fn = tri.shape[:2]
+    ts = tex.shape[2]
+    if tuple(tri.shape) != (B, Fn, 3, 3) or tuple(tex.shape) != (B, Fn, ts, ts, ts, 3):
+        raise ValueError("faces (B,F,3,3) and textures (B,F,ts,ts,ts,3) expected, got %s and %s" % (tuple(tri.shape), tuple(tex.shape)))
+    lt = None
+    if light is not None:
+        lt = keep(light).to(dev).float().contiguous()
+        if tuple(lt.shape) != (B, Fn, 3):
+            raise ValueError("light (B,F,3) expected")
+    ssaa, S = (2 if anti_aliasing else 1), int(image_size)
+    if need_grad:
+        if _lib.lib.chore_render_workspace_bytes(B, Fn, S, ssaa) == 0:
+            raise ValueError("unsupported render shape B=%d F=%d image_size=%d ssaa=%d" % (B, Fn, S, ssaa))
+        rgb, depth, alpha, fim = _RasterizeRGBAD.apply(tri, tex, lt, S, ssaa, near, far, eps, background_color)
+    else:
+        rgb, depth, alpha, fim = _render_fwd(tri, tex, lt, S, ssaa, near, far, eps, background_color, return_index)
     out = {"rgb": rgb, "depth": depth, "alpha": alpha}
     if return_index:
         out["face_index"] = fim
@@ -228,7 +301,8 @@ def rasterize_scene(faces, textures, light, points_ndc, colors=None, radius=2.0,
     if N == 0 and face_opacity is not None:        # z == far is skipped by the point rule
         pts, colors, radius, N = torch.tensor([0.0, 0.0, float(far)], device=dev).expand(B, 1, 3).contiguous(), None, 1.0, 1
     if N == 0:
-        out = rasterize_rgbad(tri, textures, light, image_size, anti_aliasing, near, far, eps, background_color, return_index)
+        out = rasterize_rgbad(tri, textures.detach(), None if light is None else light.detach(), image_size, anti_aliasing,
+                              near, far, eps, background_color, return_index)
         if return_index:
             out["sample_id"] = out.pop("face_index")
         return out
@@ -346,14 +420,14 @@ class Renderer(nn.Module):
         """what the rasteriser needs of a mesh: projected triangles, textures, light (None without textures), opacity -- with
         both windings when fill_back is set (renderer.py:119-152).  projected (B,V,3): the vertices under a camera of the
         caller's instead of this renderer's (the light always sees the world vertices)"""
-        vertices = vertices.detach().float()
+        vertices = vertices.float()           # attached: the light and the camera are torch expressions of the vertices
         faces = faces.detach()
         light = None
         if textures is None:        # coverage / depth only: one white texel cube per face
             textures = torch.ones(faces.shape[0], faces.shape[1], 2, 2, 2, 3, dtype=torch.float32, device=vertices.device)
             lit = False
         else:
-            textures = textures.detach().to(vertices.device).float()
+            textures = textures.to(vertices.device).float()
             lit = True
         if self.fill_back:
             faces = torch.cat((faces, faces.flip(-1)), dim=1)
@@ -373,7 +447,8 @@ class Renderer(nn.Module):
                                self.rasterizer_eps, self.background_color, return_index=return_index)
 
     def render(self, vertices, faces, textures, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
-        """-> (rgb (B,3,S,S), depth (B,S,S), alpha (B,S,S))   (renderer.py:237-283); inputs are detached"""
+        """-> (rgb (B,3,S,S), depth (B,S,S), alpha (B,S,S))   (renderer.py:237-283); differentiable with respect to the
+        vertices and the textures"""
         out = self._rasterize(vertices, faces, textures, (K, R, t, dist_coeffs, orig_size))
         return out["rgb"], out["depth"], out["alpha"]
 

@@ -312,7 +312,7 @@ int chore_sil_project_bwd(chore_handle* h, const float* verts, const float* obj_
                           const float* g_tri, float* d_obj_R, float* d_obj_t, float* d_obj_s, chore_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Colour / depth / coverage rendering of meshes, forward only  (replaces what Renderer.render gets from neural_renderer's
+ * Colour / depth / coverage rendering of meshes  (replaces what Renderer.render gets from neural_renderer's
  * rasterize_rgbad, external/neural_renderer/neural_renderer/rasterize.py:267-348: forward_face_index_map,
  * forward_texture_sampling, forward_background and forward_alpha_map of cuda/rasterize_cuda_kernel.cu:24-288 at image
  * size `size * ssaa`, the vertical flip and the 2x2 average of anti_aliasing=True).
@@ -333,6 +333,35 @@ size_t chore_render_workspace_bytes(int B, int F, int size, int ssaa);
 int chore_render_fwd(chore_handle* h, const float* tri, const float* textures, const float* light, int B, int F, int ts,
                      int size, int ssaa, float near_z, float far_z, float tex_eps, const float* background3, float* rgb,
                      float* depth, float* alpha, int* sample_face_index, void* workspace, chore_stream_t stream);
+/* The backward of chore_render_fwd (replaces backward_pixel_map with rgb, backward_textures and backward_depth_map,
+ * cuda/rasterize_cuda_kernel.cu:290-638, as RasterizeFunction.backward calls them, rasterize.py:114-170).  tri, textures,
+ * light, the sizes, tex_eps and background3 (HOST) are the forward's arguments, sample_face_index its output.  grad_rgb
+ * (B,3,size,size), grad_depth, grad_alpha (B,size,size): the upstream gradients, each may be NULL, and NULL gives the bits an
+ * all-zero gradient gives.  Outputs: grad_tri (B,F,3,3); grad_textures (B,F,ts,ts,ts,3) or NULL; grad_light (B,F,3) or NULL.
+ * Rules, on the sample grid S = size * ssaa:
+ *   - the upstream gradient of output pixel (r, x), divided by ssaa^2, goes to each of its samples in sample row block
+ *     size-1-r (the forward's flip and average), for rgb, depth and alpha alike;
+ *   - pixel map -> grad_tri[..., :2]: the edge walk of chore_silhouette_bwd with diff_grad = the alpha contribution plus the
+ *     three rgb contributions, summed before the diff_grad <= 0 gate; sample colours are the forward's (texel x light, or
+ *     background3), `eps` is added to the distance; back faces get nothing.  Not run when grad_rgb and grad_alpha are both
+ *     NULL (the reference's return_rgb = return_alpha = False of render_depth).  With grad_alpha alone at ssaa 1 the result
+ *     is chore_silhouette_bwd's bit for bit (its rows are not flipped: hand grad_alpha over with the rows reversed);
+ *   - depth -> grad_tri, all three components, from every sample a face won: with w the sample's weights and d its depth,
+ *     d z_k += g w_k d^2 / z_k^2 and d (x, y)_k += g w_k d^2 (S / 2) sum_l inv[3 l + (x, y)] / z_l, inv the pixel-space inverse;
+ *   - textures: the eight trilinear taps of the forward's sampling rule (clamp ts-1-tex_eps) weighted by the sample's rgb
+ *     gradient times light; light: the sample's rgb gradient times the blended texel, summed over the face's samples.
+ * Nothing is added atomically: the pixel-map term has one writer per face, the other terms are gathered per face (a
+ * workgroup walks the face's box and sums the samples it won in a fixed order), so results are bit-equal from call to call
+ * and under graph replay.  workspace: chore_render_bwd_workspace_bytes(B, F, ts, size, ssaa) bytes, 256-byte aligned, from
+ * the shapes alone (0 = unsupported shape: ssaa not 1 or 2, ts < 2, size * ssaa > 4096); it holds 36 bytes per sample.
+ * Everything runs on `stream`, nothing is allocated and no device value is read by the host, so forward + backward can be
+ * captured into one graph.  near_z / far_z are the forward's (a winner has passed them; not read). */
+size_t chore_render_bwd_workspace_bytes(int B, int F, int ts, int size, int ssaa);
+int chore_render_bwd(chore_handle* h, const float* tri, const float* textures, const float* light,
+                     const int* sample_face_index, int B, int F, int ts, int size, int ssaa, float near_z, float far_z,
+                     float tex_eps, float eps, const float* background3, const float* grad_rgb, const float* grad_depth,
+                     const float* grad_alpha, float* grad_tri, float* grad_textures, float* grad_light, void* workspace,
+                     chore_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Point clouds as shaded discs, forward only  (what the reference's -d viewer shows, recon/recon_fit_base.py:442-511,
