@@ -73,14 +73,13 @@ struct RbShared {                                      // a tile kernel's LDS
     int wcnt[4];
 };
 
-// The walk of a 256-thread workgroup (block x, y = tile, z = image) over its bin's list.  Every thread must call it; afterwards
-// the lane of output pixel (px, py) (rows not flipped; `inside` = it lies in the image) holds for each of its SS x SS
-// samples s = sy * SS + sx the winning face best[s] (-1 = none), its depth zb[s] (far_z without a face) and its weights wb[s].
-template <int SS>
-__device__ __forceinline__ void rb_walk(RbShared& sh, const TriSetup* __restrict__ ts, const int* __restrict__ count,
-                                        const int* __restrict__ list, int F, int size, float near, float far, int& px, int& py,
-                                        bool& inside, float (&zb)[SS * SS], float (&wb)[SS * SS][3], int (&best)[SS * SS]) {
-    constexpr int NS = SS * SS;
+// The staging and the hit tests of a 256-thread workgroup (block x, y = tile, z = image) over its bin's list, shared by the walks
+// below.  Every thread must call it; the lane of output pixel (px, py) (rows not flipped; `inside` = it lies in the image) calls
+// hit(s, id, zp, w) for every face id of the list that hits its sample s = sy * SS + sx, in the order of the list.
+template <int SS, class Hit>
+__device__ __forceinline__ void rb_walk_hits(RbShared& sh, const TriSetup* __restrict__ ts, const int* __restrict__ count,
+                                             const int* __restrict__ list, int F, int size, float near, float far, int& px,
+                                             int& py, bool& inside, Hit&& hit) {
     const int S = size * SS;
     const int b = blockIdx.z;
     const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
@@ -102,11 +101,6 @@ __device__ __forceinline__ void rb_walk(RbShared& sh, const TriSetup* __restrict
         const int xi = px * SS + s, yi = py * SS + s;
         xp[s] = raster_centre(xi, S); yp[s] = raster_centre(yi, S);
         xf[s] = (float)xi; yf[s] = (float)yi;
-    }
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        zb[s] = far; best[s] = -1;
-        wb[s][0] = wb[s][1] = wb[s][2] = 0.f;
     }
 
     // the aligned 16 x 16-sample tile (chore_silhouette_fwd's tile at size * ssaa) that holds this lane's samples
@@ -155,16 +149,82 @@ __device__ __forceinline__ void rb_walk(RbShared& sh, const TriSetup* __restrict
                         const int s = sy * SS + sx;
                         float w[3], zp;
                         if (!raster_hit(f, m, xp[sx], yp[sy], xf[sx], yf[sy], near, far, w, zp)) continue;
-                        // smallest depth, then smallest index: what an in-order z-buffer with `zp < depth` keeps
-                        if (zp < zb[s] || (zp == zb[s] && best[s] >= 0 && id < best[s])) {
-                            zb[s] = zp; best[s] = id;
-                            wb[s][0] = w[0]; wb[s][1] = w[1]; wb[s][2] = w[2];
-                        }
+                        hit(s, id, zp, w);
                     }
             }
         }
         __syncthreads();
     }
+}
+
+// The walk that leaves every sample's winning face in registers: afterwards the lane holds for each of its SS x SS samples
+// s = sy * SS + sx the winning face best[s] (-1 = none), its depth zb[s] (far_z without a face) and its weights wb[s].
+template <int SS>
+__device__ __forceinline__ void rb_walk(RbShared& sh, const TriSetup* __restrict__ ts, const int* __restrict__ count,
+                                        const int* __restrict__ list, int F, int size, float near, float far, int& px, int& py,
+                                        bool& inside, float (&zb)[SS * SS], float (&wb)[SS * SS][3], int (&best)[SS * SS]) {
+#pragma unroll
+    for (int s = 0; s < SS * SS; ++s) {
+        zb[s] = far; best[s] = -1;
+        wb[s][0] = wb[s][1] = wb[s][2] = 0.f;
+    }
+    rb_walk_hits<SS>(sh, ts, count, list, F, size, near, far, px, py, inside, [&](int s, int id, float zp, const float* w) {
+        // smallest depth, then smallest index: what an in-order z-buffer with `zp < depth` keeps
+        if (zp < zb[s] || (zp == zb[s] && best[s] >= 0 && id < best[s])) {
+            zb[s] = zp; best[s] = id;
+            wb[s][0] = w[0]; wb[s][1] = w[1]; wb[s][2] = w[2];
+        }
+    });
+}
+
+// A candidate (zc, fc) of group gc for one sample's list of the K nearest faces, one per group, in (zp, f) order; an empty
+// entry is (inf, -1).  The indices are compile-time constants throughout (a compare-and-shift), so the list stays in registers.
+template <int K>
+__device__ __forceinline__ void rb_layers_insert(float (&z)[K], int (&f)[K], int (&g)[K], float zc, int fc, int gc) {
+    // the group's listed face: a nearer candidate takes it out (and is inserted below), any other candidate is dropped
+    bool drop = false, shift = false;
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        if (f[i] >= 0 && g[i] == gc) {
+            if (zc < z[i] || (zc == z[i] && fc < f[i])) shift = true;
+            else drop = true;
+        }
+        if (shift) {
+            z[i] = i + 1 < K ? z[i + 1] : INFINITY;
+            f[i] = i + 1 < K ? f[i + 1] : -1;
+            g[i] = i + 1 < K ? g[i + 1] : 0;
+        }
+    }
+    if (drop) return;
+    // from the back: every entry behind the candidate moves up one place, entry K + 1 falls off.  A NaN depth compares false
+    // with every entry, the empty ones included, and is never listed (it never wins in rb_walk either)
+#pragma unroll
+    for (int i = K - 1; i >= 0; --i) {
+        if (zc < z[i] || (zc == z[i] && fc < f[i])) {
+            if (i + 1 < K) { z[i + 1] = z[i]; f[i + 1] = f[i]; g[i + 1] = g[i]; }
+            z[i] = zc; f[i] = fc; g[i] = gc;
+        }
+    }
+}
+
+// The walk that leaves every sample's K nearest faces, one per group, in registers (the rule: chore_scene_layers_fwd in
+// include/chore_hip.h): lf[s][i] (-1 = none) and their depths lz[s][i] (inf), ascending by (depth, face).  group: this image's
+// (F) group ids, or NULL = every face its own group.  The weights are not kept: raster_weights rebuilds them bit for bit.
+template <int SS, int K>
+__device__ __forceinline__ void rb_walk_layers(RbShared& sh, const TriSetup* __restrict__ ts, const int* __restrict__ count,
+                                               const int* __restrict__ list, const int* __restrict__ group, int F, int size,
+                                               float near, float far, int& px, int& py, bool& inside, float (&lz)[SS * SS][K],
+                                               int (&lf)[SS * SS][K]) {
+    int lg[SS * SS][K];
+#pragma unroll
+    for (int s = 0; s < SS * SS; ++s)
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            lz[s][i] = INFINITY; lf[s][i] = -1; lg[s][i] = 0;
+        }
+    rb_walk_hits<SS>(sh, ts, count, list, F, size, near, far, px, py, inside, [&](int s, int id, float zp, const float*) {
+        rb_layers_insert<K>(lz[s], lf[s], lg[s], zp, id, group ? group[id] : id);
+    });
 }
 
 // colour of face `face` of image b at weights w and depth z: the trilinear blend of its texture cube, times its light

@@ -8,7 +8,10 @@
 // registers; after the walk the lane loads the keys of its own SS x SS samples (at SS = 2 one 16-byte load per sample row),
 // shades both layers with the shared expressions, composes by the rule in include/chore_hip.h, resolves and stores.  The
 // super-sampled layers never reach memory.
-//   * two layers only: a translucent face shows the nearest point behind it or the background, never another face.
+//   * chore_scene_fwd composes two layers, the nearest face and the nearest point: a translucent face shows the nearest point
+//     behind it or the background.  chore_scene_layers_fwd keeps up to 8 faces per sample, optionally one per group of faces
+//     (a mesh), and composites them front to back over the point layer: scene_layers_tile_kernel, whose lists are
+//     rb_walk_layers' registers.  With one layer it launches scene_tile_kernel.
 //   * the call is a clear kernel (keys = empty, bin counters = 0; no hipMemsetAsync, whose byte-memset nodes replay
 //     unreliably in hipGraphs, see splat.hip), the setup kernel, the point pass and the tile kernel, all on the caller's
 //     stream; nothing is allocated or read back, so it can be captured.
@@ -107,6 +110,116 @@ __global__ __launch_bounds__(256) void scene_tile_kernel(const TriSetup* __restr
     }
 }
 
+// scene_tile_kernel with a list of up to `layers` <= K faces per sample, one per group, instead of the one winner
+// (chore_scene_layers_fwd's rule).  The lists live in registers from the walk to the blend and never reach memory.  Only the
+// v visible layers are shaded, back to front, in a loop that is NOT unrolled: it picks layer i out of the registers by a chain of
+// selects over compile-time indices, so the shading code exists once per sample and nothing is indexed dynamically.
+template <int SS, int K>
+__global__ __launch_bounds__(256) void scene_layers_tile_kernel(
+    const TriSetup* __restrict__ ts, const int* __restrict__ count, const int* __restrict__ list, const float* __restrict__ textures,
+    const float* __restrict__ light, const float* __restrict__ face_opacity, const int* __restrict__ face_group, int layers, int F,
+    int tsz, const unsigned long long* __restrict__ keys, const float* __restrict__ pts, const float* __restrict__ colors,
+    const float* __restrict__ radius, float radius_px, int N, float bias, int size, float ambient, float near, float far,
+    float tex_eps, float bg0, float bg1, float bg2, float* __restrict__ rgb, float* __restrict__ depth_out,
+    float* __restrict__ alpha_out, int* __restrict__ sample_id) {
+    constexpr int NS = SS * SS;
+    __shared__ RbShared sh;
+    const int S = size * SS;
+    const int b = blockIdx.z;
+    const TriSetup* tsb = ts + (size_t)b * F;
+    int px, py;
+    bool inside;
+    float lz[NS][K];
+    int lf[NS][K];
+    rb_walk_layers<SS, K>(sh, ts, count, list, face_group ? face_group + (size_t)b * F : nullptr, F, size, near, far, px, py, inside,
+                          lz, lf);
+    if (!inside) return;
+
+    unsigned long long k[NS];
+    sp_load_keys<SS>(keys + (size_t)b * S * S, S, px, py, k);
+    const float Sf = (float)S;
+    const float direct = __fsub_rn(1.f, ambient);
+    const float* opb = face_opacity ? face_opacity + (size_t)b * F : nullptr;
+    auto opacity = [&](int f) { return opb ? fminf(fmaxf(opb[f], 0.f), 1.f) : 1.f; };      // NaN -> 0
+    float acc[3] = {0.f, 0.f, 0.f}, zacc = 0.f, aacc = 0.f;
+    int id[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        float c[3] = {bg0, bg1, bg2}, z = far, a = 0.f;
+        id[s] = -1;
+        const bool pt = k[s] != SP_EMPTY;
+        if (pt) {                       // `c` becomes the point's colour: what shows if it is in front, and under the faces if not
+            const unsigned n = (unsigned)k[s];
+            sp_shade(pts, colors, radius, radius_px, SS, Sf, near, far, (size_t)b * N + n, px * SS + (s % SS),
+                     py * SS + (s / SS), ambient, direct, c, z);
+            a = 1.f;
+            id[s] = -2 - (int)n;
+        }
+        // j listed faces lie before the point (equality goes to the face); depths ascend, so they are the first j
+        const float zt = __fsub_rn(z, bias);
+        int j = 0;
+#pragma unroll
+        for (int q = 0; q < K; ++q)
+            if (q < layers && lf[s][q] >= 0 && !(pt && zt < lz[s][q])) j = q + 1;
+        // v of them are visible: up to the first opaque one
+        int v = j;
+        bool cut = false;
+#pragma unroll
+        for (int q = 0; q < K; ++q)
+            if (q < j && !cut && opacity(lf[s][q]) >= 1.f) {
+                v = q + 1;
+                cut = true;
+            }
+        if (v > 0) {
+            const int xi = px * SS + (s % SS), yi = py * SS + (s / SS);
+            float al = 0.f;
+#pragma unroll 1
+            for (int i = v - 1; i >= 0; --i) {
+                float zi = lz[s][0];
+                int fi = lf[s][0];
+#pragma unroll
+                for (int q = 1; q < K; ++q)
+                    if (q == i) {
+                        zi = lz[s][q];
+                        fi = lf[s][q];
+                    }
+                const float* tf = reinterpret_cast<const float*>(tsb + fi);
+                float w[3], zr, m[3];
+                raster_weights(tf, tf + 9, (float)xi, (float)yi, w, zr);       // the walk's own expressions: zr == zi
+                rb_shade(tsb, textures, light, b, F, fi, tsz, tex_eps, w, zi, m);
+                const float o = opacity(fi), u = __fsub_rn(1.f, o);
+                if (o >= 1.f) {
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) c[q] = m[q];
+                } else {
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) c[q] = __fadd_rn(__fmul_rn(o, m[q]), __fmul_rn(u, c[q]));
+                }
+                al = __fadd_rn(o, __fmul_rn(u, al));
+            }
+            z = lz[s][0];
+            a = (pt || cut) ? 1.f : al;
+            id[s] = lf[s][0];
+        }
+#pragma unroll
+        for (int q = 0; q < 3; ++q) acc[q] += c[q];
+        zacc += z;
+        aacc += a;
+    }
+    constexpr float inv_ns = 1.f / NS;
+    const int row = size - 1 - py;                        // the flip of chore_render_fwd
+    const size_t plane = (size_t)size * size, o = (size_t)row * size + px;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) rgb[((size_t)b * 3 + q) * plane + o] = acc[q] * inv_ns;
+    depth_out[(size_t)b * plane + o] = zacc * inv_ns;
+    alpha_out[(size_t)b * plane + o] = aacc * inv_ns;
+    if (sample_id) {
+#pragma unroll
+        for (int s = 0; s < NS; ++s)
+            sample_id[((size_t)b * S + (py * SS + s / SS)) * S + (px * SS + s % SS)] = id[s];
+    }
+}
+
 }  // namespace
 
 extern "C" size_t chore_scene_workspace_bytes(int B, int F, int N, int size, int ssaa) {
@@ -115,26 +228,27 @@ extern "C" size_t chore_scene_workspace_bytes(int B, int F, int N, int size, int
     return rb_align(rb) + splat_key_bytes(B, size, ssaa);
 }
 
-extern "C" int chore_scene_fwd(chore_handle* h, const float* tri, const float* textures, const float* light,
-                               const float* face_opacity, int B, int F, int ts, const float* pts, const float* point_rgb,
-                               const float* radius, float radius_px, int N, float point_depth_bias, int size, int ssaa,
-                               float ambient, float near_z, float far_z, float tex_eps, const float* background3, float* rgb,
-                               float* depth, float* alpha, int* sample_id, void* workspace, chore_stream_t stream) {
+// both entry points: the checks, the three shared passes and the tile kernel for `layers` (1 = scene_tile_kernel)
+static int scene_fwd(chore_handle* h, const char* who, const float* tri, const float* textures, const float* light,
+                     const float* face_opacity, int B, int F, int ts, const float* pts, const float* point_rgb, const float* radius,
+                     float radius_px, int N, float point_depth_bias, int size, int ssaa, float ambient, float near_z, float far_z,
+                     float tex_eps, const float* background3, const int* face_group, int layers, float* rgb, float* depth,
+                     float* alpha, int* sample_id, void* workspace, chore_stream_t stream) {
     CHORE_ENTER(h);
     if (!tri || !textures || !pts || !background3 || !rgb || !depth || !alpha || !workspace)
-        CHORE_FAIL(h, CHORE_EINVAL, "chore_scene_fwd: null argument");
-    if (ssaa != 1 && ssaa != 2) CHORE_FAIL(h, CHORE_EINVAL, "chore_scene_fwd: ssaa must be 1 or 2, got %d", ssaa);
+        CHORE_FAIL(h, CHORE_EINVAL, "%s: null argument", who);
+    if (layers < 1 || layers > 8) CHORE_FAIL(h, CHORE_EINVAL, "%s: face_layers must lie in 1..8, got %d", who, layers);
+    if (ssaa != 1 && ssaa != 2) CHORE_FAIL(h, CHORE_EINVAL, "%s: ssaa must be 1 or 2, got %d", who, ssaa);
     if (!render_shape_ok(B, F, ts, size, ssaa) || !splat_shape_ok(B, N, size, ssaa))
-        CHORE_FAIL(h, CHORE_EINVAL, "chore_scene_fwd: bad sizes B=%d F=%d ts=%d N=%d size=%d ssaa=%d", B, F, ts, N, size, ssaa);
+        CHORE_FAIL(h, CHORE_EINVAL, "%s: bad sizes B=%d F=%d ts=%d N=%d size=%d ssaa=%d", who, B, F, ts, N, size, ssaa);
     if (!(ambient >= 0.f && ambient <= 1.f))
-        CHORE_FAIL(h, CHORE_EINVAL, "chore_scene_fwd: ambient must lie in [0, 1], got %g", (double)ambient);
+        CHORE_FAIL(h, CHORE_EINVAL, "%s: ambient must lie in [0, 1], got %g", who, (double)ambient);
     if (!(near_z < far_z))
-        CHORE_FAIL(h, CHORE_EINVAL, "chore_scene_fwd: near_z %g must be below far_z %g", (double)near_z, (double)far_z);
+        CHORE_FAIL(h, CHORE_EINVAL, "%s: near_z %g must be below far_z %g", who, (double)near_z, (double)far_z);
     if (!radius && !(radius_px > 0.f))
-        CHORE_FAIL(h, CHORE_EINVAL, "chore_scene_fwd: radius_px must be positive without per-point radii, got %g",
-                   (double)radius_px);
+        CHORE_FAIL(h, CHORE_EINVAL, "%s: radius_px must be positive without per-point radii, got %g", who, (double)radius_px);
     if (!(point_depth_bias >= 0.f))
-        CHORE_FAIL(h, CHORE_EINVAL, "chore_scene_fwd: point_depth_bias must be >= 0, got %g", (double)point_depth_bias);
+        CHORE_FAIL(h, CHORE_EINVAL, "%s: point_depth_bias must be >= 0, got %g", who, (double)point_depth_bias);
     hipStream_t s = (hipStream_t)stream;
     const int S = size * ssaa, nb = rb_bins(S), total = B * N, nf = B * F;
     const RenderWs w = render_ws(workspace, B, F, S);
@@ -149,14 +263,41 @@ extern "C" int chore_scene_fwd(chore_handle* h, const float* tri, const float* t
                        ssaa, near_z, far_z, keys);
     CHORE_LAUNCH_CHECK(h, s);
     const dim3 grid((size + RB_TW - 1) / RB_TW, (size + RB_TH - 1) / RB_TH, B);
-    if (ssaa == 2)
-        hipLaunchKernelGGL(scene_tile_kernel<2>, grid, dim3(256), 0, s, w.ts, w.count, w.list, textures, light, face_opacity, F, ts,
-                           keys, pts, point_rgb, radius, radius_px, N, point_depth_bias, size, ambient, near_z, far_z, tex_eps,
+    if (layers == 1) {
+        const auto kernel = ssaa == 2 ? scene_tile_kernel<2> : scene_tile_kernel<1>;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, w.ts, w.count, w.list, textures, light, face_opacity, F, ts, keys, pts,
+                           point_rgb, radius, radius_px, N, point_depth_bias, size, ambient, near_z, far_z, tex_eps, background3[0],
+                           background3[1], background3[2], rgb, depth, alpha, sample_id);
+    } else {
+        // capacities 2, 4 and 8; a request between two of them runs in the larger with its list cut at `layers`
+        const auto kernel = layers <= 2 ? (ssaa == 2 ? scene_layers_tile_kernel<2, 2> : scene_layers_tile_kernel<1, 2>)
+                          : layers <= 4 ? (ssaa == 2 ? scene_layers_tile_kernel<2, 4> : scene_layers_tile_kernel<1, 4>)
+                                        : (ssaa == 2 ? scene_layers_tile_kernel<2, 8> : scene_layers_tile_kernel<1, 8>);
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, w.ts, w.count, w.list, textures, light, face_opacity, face_group, layers, F,
+                           ts, keys, pts, point_rgb, radius, radius_px, N, point_depth_bias, size, ambient, near_z, far_z, tex_eps,
                            background3[0], background3[1], background3[2], rgb, depth, alpha, sample_id);
-    else
-        hipLaunchKernelGGL(scene_tile_kernel<1>, grid, dim3(256), 0, s, w.ts, w.count, w.list, textures, light, face_opacity, F, ts,
-                           keys, pts, point_rgb, radius, radius_px, N, point_depth_bias, size, ambient, near_z, far_z, tex_eps,
-                           background3[0], background3[1], background3[2], rgb, depth, alpha, sample_id);
+    }
     CHORE_LAUNCH_CHECK(h, s);
     return CHORE_OK;
+}
+
+extern "C" int chore_scene_fwd(chore_handle* h, const float* tri, const float* textures, const float* light,
+                               const float* face_opacity, int B, int F, int ts, const float* pts, const float* point_rgb,
+                               const float* radius, float radius_px, int N, float point_depth_bias, int size, int ssaa,
+                               float ambient, float near_z, float far_z, float tex_eps, const float* background3, float* rgb,
+                               float* depth, float* alpha, int* sample_id, void* workspace, chore_stream_t stream) {
+    return scene_fwd(h, "chore_scene_fwd", tri, textures, light, face_opacity, B, F, ts, pts, point_rgb, radius, radius_px, N,
+                     point_depth_bias, size, ssaa, ambient, near_z, far_z, tex_eps, background3, nullptr, 1, rgb, depth, alpha,
+                     sample_id, workspace, stream);
+}
+
+extern "C" int chore_scene_layers_fwd(chore_handle* h, const float* tri, const float* textures, const float* light,
+                                      const float* face_opacity, int B, int F, int ts, const float* pts, const float* point_rgb,
+                                      const float* radius, float radius_px, int N, float point_depth_bias, int size, int ssaa,
+                                      float ambient, float near_z, float far_z, float tex_eps, const float* background3,
+                                      const int* face_group, int face_layers, float* rgb, float* depth, float* alpha,
+                                      int* sample_id, void* workspace, chore_stream_t stream) {
+    return scene_fwd(h, "chore_scene_layers_fwd", tri, textures, light, face_opacity, B, F, ts, pts, point_rgb, radius, radius_px,
+                     N, point_depth_bias, size, ssaa, ambient, near_z, far_z, tex_eps, background3, face_group, face_layers, rgb,
+                     depth, alpha, sample_id, workspace, stream);
 }

@@ -554,6 +554,9 @@ class ReconFitterBase:
     # behind a surface and still be drawn in front of it -- the generated points lie ON the surfaces they were fitted to
     VIEW_MESH_OPACITY, VIEW_GT_OPACITY, VIEW_POINT_BIAS = 0.6, 0.35, 0.02
     VIEW_CENTRE_R = 0.06                          # the centre markers of visualize_fit_scene: sphere meshes, metres
+    # visualize_fit_scene: how many meshes a sample shows through each other (Renderer.render_scene's face_layers, one layer per
+    # mesh).  1 = a translucent mesh hides every mesh behind it; set it to 4, say, to see the object through the body
+    VIEW_FACE_LAYERS = 1
     _view_index = 0
     debug_dest = None                             # (save_name, test_id) of the debug files; fit_recon sets it from its args
 
@@ -625,9 +628,13 @@ class ReconFitterBase:
         the centres `obj_center_pred` (cyan), `smpl_center_pred` (yellow), `smpl_center_act` (magenta) as opaque 6 cm sphere
         meshes; `hum_gt` / `obj_gt` (objects with verts_list() / faces_list(), as the reference reads them) white and more
         translucent; the keypoints -> (512, 1152, 3) uint8.
-        A translucent face never shows another face, so a centre sphere inside a fitted mesh -- where the centres of a good
-        fit lie -- is hidden by it.  Each centre is therefore ALSO a disc of the same radius at the centre's depth: a point, which
-        the translucent mesh in front of it does show (blended), and which its own sphere covers wherever the sphere is visible."""
+        With VIEW_FACE_LAYERS = 1 (the default) a translucent face never shows another face, so a centre sphere inside a fitted
+        mesh -- where the centres of a good fit lie -- is hidden by it.  Each centre is therefore ALSO a disc of the same radius at
+        the centre's depth: a point, which the translucent mesh in front of it does show (blended), and which its own sphere
+        covers wherever the sphere is visible.
+        With VIEW_FACE_LAYERS = K > 1 (set it on the fitter or its class before fitting with -d) every sample composites its K
+        nearest meshes front to back, each mesh one layer (chore_scene_layers_fwd with the mesh index as face group): the object,
+        the ground-truth meshes and the centre spheres show through the body, and the duplicate discs are left out."""
         from ..utils.render_utils import (CLOUD_VIEW_SIZE, SMPL_OBJ_COLOR_LIST, Mesh, icosphere_mesh, render_scene_views)
         idx = self._view_index
         host = lambda x: np.asarray(x.detach().cpu()) if torch.is_tensor(x) else np.asarray(x)     # noqa: E731
@@ -654,7 +661,7 @@ class ReconFitterBase:
         clouds, colors, radii = [], [], []
         for key, colour in (("obj_center_pred", self.VIEW_CYAN), ("smpl_center_pred", self.VIEW_YELLOW),
                             ("smpl_center_act", self.VIEW_MAGENTA)):
-            if key in data_dict:
+            if key in data_dict and self.VIEW_FACE_LAYERS <= 1:
                 clouds.append(data_dict[key][idx].detach().reshape(1, 3))
                 colors.append(colour)
                 radii.append(self.VIEW_CENTRE_R)
@@ -675,7 +682,8 @@ class ReconFitterBase:
         if "body_kpts" in data_dict:                          # detected keypoints
             markers.append((data_dict["body_kpts"][idx][:, :2] * (CLOUD_VIEW_SIZE / float(self.net_in_size)), self.VIEW_RED, 2.0))
         return render_scene_views(data_dict["images"][idx], crop_center[idx], meshes, mesh_colors, opacity, clouds, colors, radii,
-                                  markers, point_depth_bias=self.VIEW_POINT_BIAS, camera=self.camera)
+                                  markers, point_depth_bias=self.VIEW_POINT_BIAS, camera=self.camera,
+                                  face_layers=self.VIEW_FACE_LAYERS)
 
     def _contact_view_data(self, data_dict, model, obj_center_pred, object, smpl, smpl_verts):
         """what visualize_contact_fitting adds to data_dict for the whole batch: the contact masks (two field queries) and the

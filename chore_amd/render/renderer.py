@@ -269,12 +269,15 @@ def splat_points(points_ndc, colors=None, radius=2.0, image_size=256, anti_alias
 
 def rasterize_scene(faces, textures, light, points_ndc, colors=None, radius=2.0, face_opacity=None, point_depth_bias=0.0,
                     image_size=256, anti_aliasing=True, near=DEFAULT_NEAR, far=DEFAULT_FAR, eps=DEFAULT_EPS, ambient=0.6,
-                    background_color=(0, 0, 0), return_index=False):
+                    background_color=(0, 0, 0), return_index=False, face_layers=1, face_group=None):
     """meshes and point clouds in ONE image, depth-tested against each other per sample before the anti-aliasing average
     (chore_scene_fwd; the rule is written down in include/chore_hip.h).  faces / textures / light as `rasterize_rgbad` takes
-    them, points_ndc / colors / radius as `splat_points` does; face_opacity (B,F) in [0,1] or None = opaque: a translucent face
-    shows the nearest point behind it or the background, never another face; point_depth_bias >= 0 (depth units) lets a point
-    that lies ON a surface win against it.
+    them, points_ndc / colors / radius as `splat_points` does; face_opacity (B,F) in [0,1] or None = opaque; point_depth_bias
+    >= 0 (depth units) lets a point that lies ON a surface win against it.
+    face_layers (1..8): how many faces a sample composites front to back.  With the default 1 a translucent face shows the
+    nearest point behind it or the background, never another face; with more (chore_scene_layers_fwd) it shows the faces
+    behind it too, down to the first opaque one or the point.  face_group (B,F) integers or None: of the faces with one group id
+    only the nearest counts, so a translucent closed mesh given as one group adds one layer and not also its own back side.
     -> dict(rgb (B,3,S,S), depth (B,S,S), alpha (B,S,S)[, sample_id (B,S*ssaa,S*ssaa) int32, rows not flipped: f >= 0 a face,
     -2 - n a point, -1 nothing]).  F == 0 is `splat_points`; N == 0 is `rasterize_rgbad` when every face is opaque, and the
     scene kernel with one point that is never drawn when there is a face_opacity to honour."""
@@ -283,6 +286,9 @@ def rasterize_scene(faces, textures, light, points_ndc, colors=None, radius=2.0,
     bias = float(point_depth_bias)
     if not bias >= 0.0:
         raise ValueError("point_depth_bias must be >= 0, got %r" % (point_depth_bias,))
+    layers = int(face_layers)
+    if not 1 <= layers <= 8:
+        raise ValueError("face_layers must lie in 1..8, got %r" % (face_layers,))
     dev = faces.device
     tri = faces.detach().float().contiguous()
     pts = points_ndc.detach().to(dev).float().contiguous()
@@ -292,6 +298,11 @@ def rasterize_scene(faces, textures, light, points_ndc, colors=None, radius=2.0,
         raise ValueError("faces (B,F,3,3) and points_ndc (B,N,3) of one batch size expected, got %s and %s"
                          % (tuple(tri.shape), tuple(pts.shape)))
     B, Fn, N = tri.shape[0], tri.shape[1], pts.shape[1]
+    grp = None
+    if face_group is not None:
+        if torch.is_floating_point(face_group) or tuple(face_group.shape) != (B, Fn):
+            raise ValueError("face_group: integers %s expected, got %s %s" % ((B, Fn), face_group.dtype, tuple(face_group.shape)))
+        grp = face_group.detach().to(dev).to(torch.int32).contiguous()
     if Fn == 0:
         out = splat_points(pts, colors, radius, image_size, anti_aliasing, near, far, ambient, background_color, return_index)
         if return_index:
@@ -337,10 +348,13 @@ def rasterize_scene(faces, textures, light, points_ndc, colors=None, radius=2.0,
     sid = torch.empty(B, S * ssaa, S * ssaa, dtype=torch.int32, device=dev) if return_index else None
     bg = (ctypes.c_float * 3)(*[float(c) for c in background_color])
     ptr = lambda x: x.data_ptr() if x is not None else None      # noqa: E731
-    _lib.check(_lib.lib.chore_scene_fwd(h, tri.data_ptr(), tex.data_ptr(), ptr(lt), ptr(op), B, Fn, ts, pts.data_ptr(), ptr(col),
-                                        ptr(rad), radius_px, N, bias, S, ssaa, float(ambient), float(near), float(far),
-                                        float(eps), bg, rgb.data_ptr(), depth.data_ptr(), alpha.data_ptr(), ptr(sid),
-                                        ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), h, "chore_scene_fwd")
+    head = (h, tri.data_ptr(), tex.data_ptr(), ptr(lt), ptr(op), B, Fn, ts, pts.data_ptr(), ptr(col), ptr(rad), radius_px, N, bias, S,
+            ssaa, float(ambient), float(near), float(far), float(eps), bg)
+    tail = (rgb.data_ptr(), depth.data_ptr(), alpha.data_ptr(), ptr(sid), ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    if layers == 1 and grp is None:
+        _lib.check(_lib.lib.chore_scene_fwd(*head, *tail), h, "chore_scene_fwd")
+    else:
+        _lib.check(_lib.lib.chore_scene_layers_fwd(*head, ptr(grp), layers, *tail), h, "chore_scene_layers_fwd")
     out = {"rgb": rgb, "depth": depth, "alpha": alpha}
     if return_index:
         out["sample_id"] = sid
@@ -495,16 +509,22 @@ class Renderer(nn.Module):
         return ndc, radius
 
     def render_scene(self, vertices, faces, textures, points, colors=None, radius=2.0, world_radius=None, face_opacity=None,
-                     point_depth_bias=0.0, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
+                     point_depth_bias=0.0, K=None, R=None, t=None, dist_coeffs=None, orig_size=None, face_layers=1,
+                     face_group=None):
         """a mesh (as `render` takes it) and world points (as `render_points` takes them) in one image, occluding each other
         per sample -> (rgb (B,3,S,S), depth (B,S,S), alpha (B,S,S)); inputs are detached.  face_opacity (B,F) or None =
-        opaque, per face of `faces` (both windings get it under fill_back); point_depth_bias: see `rasterize_scene`."""
+        opaque, and face_group (B,F) integers or None, per face of `faces` (both windings get them under fill_back);
+        point_depth_bias, face_layers, face_group: see `rasterize_scene`."""
         cam = (K, R, t, dist_coeffs, orig_size)
+        if face_group is not None:
+            face_group = torch.as_tensor(face_group).to(vertices.device)
+            if self.fill_back:
+                face_group = torch.cat((face_group, face_group), dim=1)
         if face_opacity is not None:
             face_opacity = torch.as_tensor(face_opacity, dtype=torch.float32).to(vertices.device)
         tri, textures, light, face_opacity = self._prepare_faces(vertices, faces, textures, cam, face_opacity)
         ndc, radius = self._prepare_points(points.to(vertices.device), radius, world_radius, cam)
         out = rasterize_scene(tri, textures, light, ndc, colors, radius, face_opacity, point_depth_bias, self.image_size,
                               self.anti_aliasing, self.near, self.far, self.rasterizer_eps,
-                              background_color=self.background_color)
+                              background_color=self.background_color, face_layers=face_layers, face_group=face_group)
         return out["rgb"], out["depth"], out["alpha"]

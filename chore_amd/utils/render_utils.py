@@ -191,16 +191,18 @@ class NrWrapper:
         return rgb[0].permute(1, 2, 0).clamp(0, 1).cpu().numpy(), alpha[0].cpu().numpy()
 
     def render_scene(self, renderer, meshes, clouds, colors, world_radius, mesh_colors=None, mesh_opacity=1.0,
-                     point_depth_bias=0.0):
+                     point_depth_bias=0.0, face_layers=1):
         """meshes and point clouds in ONE scene call, occluding each other per sample: meshes / mesh_colors as `render_meshes`
         takes them, mesh_opacity one number for all or one per mesh, clouds / colors / world_radius as `render_points` does,
-        point_depth_bias in metres (Renderer.render_scene).  -> image (S,S,3) float in [0,1], coverage (S,S) float in [0,1]"""
+        point_depth_bias in metres (Renderer.render_scene); face_layers > 1: a translucent mesh shows up to that many meshes, the
+        nearest face of each (`mesh_face_group`).  -> image (S,S,3) float in [0,1], coverage (S,S) float in [0,1]"""
         verts, faces, textures = self.prepare_render(meshes, mesh_colors)
         pts, col, rad = concat_clouds(clouds, colors, world_radius, self.device)
+        used = self.colors if mesh_colors is None else mesh_colors
         rgb, _, alpha = renderer.render_scene(verts, faces, textures, pts[None], col[None], world_radius=rad[None],
-                                              face_opacity=mesh_face_opacity(meshes, mesh_opacity, self.device,
-                                                                             self.colors if mesh_colors is None else mesh_colors),
-                                              point_depth_bias=point_depth_bias)
+                                              face_opacity=mesh_face_opacity(meshes, mesh_opacity, self.device, used),
+                                              point_depth_bias=point_depth_bias, face_layers=face_layers,
+                                              face_group=mesh_face_group(meshes, self.device, used) if face_layers > 1 else None)
         return rgb[0].permute(1, 2, 0).clamp(0, 1).cpu().numpy(), alpha[0].cpu().numpy()
 
     def prepare_side_rend(self, meshes, maxd=1.5, colors=None):
@@ -252,6 +254,14 @@ def mesh_face_opacity(meshes, mesh_opacity, device, colors=None):
         raise ValueError("%d meshes need %d opacities (got %d) and as many colours (got %s)"
                          % (len(meshes), len(meshes), len(mesh_opacity), "none" if colors is None else len(colors)))
     return torch.cat([torch.full((len(m.f),), float(o), device=device) for m, o in zip(meshes, mesh_opacity)])[None]
+
+
+def mesh_face_group(meshes, device, colors=None):
+    """the mesh index of every face -> (1, sum F) int32, in the face order of `mesh_tensors`: the `face_group` under which a
+    translucent mesh counts as ONE layer of the scene rasteriser.  `colors` as in `mesh_face_opacity`"""
+    if colors is not None and len(colors) < len(meshes):
+        raise ValueError("%d meshes need as many colours (got %d)" % (len(meshes), len(colors)))
+    return torch.cat([torch.full((len(m.f),), i, dtype=torch.int32, device=device) for i, m in enumerate(meshes)])[None]
 
 
 def concat_clouds(clouds, colors, radii, device):
@@ -358,13 +368,14 @@ def render_cloud_views(images_b, crop_center_b, clouds, colors, radii, markers2d
 
 
 def render_scene_views(images_b, crop_center_b, meshes, mesh_colors, mesh_opacity, clouds, colors, radii, markers2d=None,
-                       point_depth_bias=0.0, side_renderer=None, camera=None, maxd=1.5, min_radius_px=1.0):
+                       point_depth_bias=0.0, side_renderer=None, camera=None, maxd=1.5, min_radius_px=1.0, face_layers=1):
     """meshes AND point clouds of ONE frame in the two views of `render_cloud_views` -> (512, 512 + 640, 3) uint8, each view one
     scene call (chore_scene_fwd), so meshes and points occlude each other per sample.
 
-    meshes with .v (camera space) / .f, mesh_colors one colour each, mesh_opacity one number for all or one per mesh (a
-    translucent face shows the nearest point behind it or the background, never another face); point_depth_bias in metres
-    (scaled with the side view); the rest as `render_cloud_views` takes it.  The meshes go through exactly the clouds'
+    meshes with .v (camera space) / .f, mesh_colors one colour each, mesh_opacity one number for all or one per mesh.  With
+    face_layers = 1 a translucent face shows the nearest point behind it or the background, never another face; with
+    face_layers > 1 (chore_scene_layers_fwd) a translucent mesh shows up to that many meshes, each as one layer: the mesh index
+    is the face group.  point_depth_bias in metres (scaled with the side view); the rest as `render_cloud_views` takes it.  The meshes go through exactly the clouds'
     transforms: the network's camera with v = -ny in the input view (lit like setup_renderer's front view), and in the side
     view the y-flip, scale and centring, which are computed from the cloud points and the mesh vertices together."""
     if not meshes:
@@ -374,6 +385,9 @@ def render_scene_views(images_b, crop_center_b, meshes, mesh_colors, mesh_opacit
     pts, col, rad = concat_clouds(clouds, colors, radii, dev)
     verts, faces, textures = mesh_tensors(meshes, mesh_colors, dev)
     opacity = mesh_face_opacity(meshes, mesh_opacity, dev, mesh_colors)
+    group = mesh_face_group(meshes, dev, mesh_colors) if face_layers > 1 else None
+    # both windings of a face get its group where a renderer fills the back, as they get its opacity
+    wound = lambda r: torch.cat((group, group), dim=1) if group is not None and r.fill_back else group      # noqa: E731
     S, near, far = CLOUD_VIEW_SIZE, nr.renderer.DEFAULT_NEAR, nr.renderer.DEFAULT_FAR
     ndc = _input_view_ndc(camera, pts, crop_center_b)
     focal = camera.fx_px * S / camera.crop_size
@@ -383,7 +397,8 @@ def render_scene_views(images_b, crop_center_b, meshes, mesh_colors, mesh_opacit
     front_light = _soft_light(nr.Renderer(camera_mode='look_at', image_size=S), 0.4, [1, 0.5, 1])      # carries the light only
     tri, tex, light, op = front_light._prepare_faces(verts, faces, textures, (), opacity,
                                                      projected=_input_view_ndc(camera, verts[0], crop_center_b))
-    out = nr.rasterize_scene(tri, tex, light, ndc, col[None], rad_px, op, point_depth_bias, S, True, near, far, ambient=0.6)
+    out = nr.rasterize_scene(tri, tex, light, ndc, col[None], rad_px, op, point_depth_bias, S, True, near, far, ambient=0.6,
+                             face_layers=face_layers, face_group=wound(front_light))
     front = _over_photo(out, images_b, S)
 
     side_renderer = setup_side_renderer(2.0, 0., 90.) if side_renderer is None else side_renderer
@@ -394,7 +409,8 @@ def render_scene_views(images_b, crop_center_b, meshes, mesh_colors, mesh_opacit
     rgb = nr.rasterize_scene(tri, tex, light, side_ndc, col[None, :n], side_px.clamp(min=min_radius_px), op,
                              float(point_depth_bias * scale), side_renderer.image_size, side_renderer.anti_aliasing,
                              side_renderer.near, side_renderer.far, side_renderer.rasterizer_eps,
-                             background_color=side_renderer.background_color)["rgb"]
+                             background_color=side_renderer.background_color, face_layers=face_layers,
+                             face_group=wound(side_renderer))["rgb"]
     return np.concatenate([front, _side_crop(rgb, S)], axis=1)
 
 

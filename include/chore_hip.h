@@ -411,7 +411,8 @@ int chore_splat_fwd(chore_handle* h, const float* pts, const float* rgb_in, cons
  *     untouched when o >= 1, otherwise o * m + (1 - o) * under (two products, one sum); depth zf; alpha 1 where a point
  *     covers the sample, otherwise o; sample_id = f;
  *   - nothing covers the sample: background3 / far_z / 0, sample_id = -1.
- * Two layers only: a translucent face shows the nearest point behind it or the background, never another face.
+ * Two layers are the default, not the limit: here a translucent face shows the nearest point behind it or the background;
+ * chore_scene_layers_fwd (below) lets it show further faces as well.
  * Outputs are resolved as chore_render_fwd's and chore_splat_fwd's: per output pixel the samples are summed in the order
  * s = sy * ssaa + sx starting from 0 and multiplied by 1 / ssaa^2, for rgb (B,3,size,size), depth (B,size,size) and alpha
  * (B,size,size) alike; row r holds the sample rows of block size-1-r.  sample_id (B,size*ssaa,size*ssaa) int32 or NULL, rows
@@ -427,6 +428,45 @@ int chore_scene_fwd(chore_handle* h,
     const float* tri, const float* textures, const float* light, const float* face_opacity, int B, int F, int ts,
     const float* pts, const float* point_rgb, const float* radius, float radius_px, int N, float point_depth_bias,
     int size, int ssaa, float ambient, float near_z, float far_z, float tex_eps, const float* background3,
+    float* rgb, float* depth, float* alpha, int* sample_id, void* workspace, chore_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * chore_scene_fwd with several face layers: per sample a list of up to K = face_layers faces (1 <= K <= 8) is composited
+ * front to back with the point layer and the background, so that a translucent mesh shows the meshes behind it.  The arguments
+ * are chore_scene_fwd's plus face_group (B,F) int32 or NULL and face_layers.  g(f) = face_group[b,f] (any int32) when
+ * face_group is given, otherwise g(f) = f: of the faces of one group only the nearest counts, so a translucent closed mesh
+ * that is one group adds one layer and not also its own back side.
+ * Per sample of the size * ssaa grid, all arithmetic fp32, each operation rounded once, in the association written here:
+ *   1. candidates: every face that hits the sample under chore_render_fwd's hit rule (the aligned 16 x 16 tile box test of
+ *      chore_silhouette_fwd included), with its depth zp.  A NaN zp is no candidate (it never wins in chore_render_fwd);
+ *   2. grouping: of the candidates with equal g, the one with the smallest zp, then the smallest f, is kept;
+ *   3. ordering: the survivors are ordered by (zp, f) ascending and the first K kept: e_1 .. e_m with depths z_i, faces f_i,
+ *      colours m_i (texture blend times light, as chore_render_fwd) and opacities o_i = fminf(fmaxf(face_opacity[b,f_i], 0), 1),
+ *      NaN -> 0, NULL = 1;
+ *   4. the point layer is exactly chore_splat_fwd's: the winner n, its shaded colour p, its depth zn;
+ *   5. e_i lies before the point iff not (a point covers the sample and zn - point_depth_bias < z_i); equality goes to the
+ *      face.  Depths ascend, so these are a prefix e_1 .. e_j;
+ *   6. the cut: v = the first i <= j with o_i >= 1, or j if there is none;
+ *   7. v = 0: the point gives p / zn / 1 / sample_id -2 - n; without a point background3 / far_z / 0 / -1;
+ *   8. v >= 1: under = p where a point covers the sample, otherwise background3.  Colour: c = under, then for i = v down to 1:
+ *      c = m_i if o_i >= 1, else o_i * m_i + (1 - o_i) * c (two products, one sum).  depth = z_1, sample_id = f_1.
+ *      alpha = 1 where a point covers the sample or o_v >= 1; otherwise a = 0, then for i = v down to 1: a = o_i + (1 - o_i) * a;
+ *   9. resolve, flip and sample_id layout as chore_scene_fwd's.
+ * Consequences: K = 1 is chore_scene_fwd's rule, with or without groups (the alpha fold gives o + (1 - o) * 0 = o), and runs
+ * chore_scene_fwd's kernel.  Faces beyond the K nearest, faces behind the point and faces behind the first opaque face do not
+ * exist for the sample.  A face of opacity 0 still takes a layer.  The result does not depend on the order in which the faces
+ * are met (the kernel streams: a sorted list of K entries per sample in registers; a candidate of a listed group replaces
+ * that entry if it is nearer by (zp, f) and is dropped otherwise, a candidate of a new group is inserted and entry K + 1 falls
+ * off; the K-th depth never grows, so this keeps what steps 1-3 keep).
+ * workspace: chore_scene_workspace_bytes, unchanged: the lists never reach memory.  The launches are chore_scene_fwd's, all
+ * on `stream`; nothing is allocated or read back, so the call can be captured into a graph.
+ * CHORE_EINVAL, before anything is launched: face_layers outside 1..8 and whatever chore_scene_fwd refuses.
+ * ------------------------------------------------------------------------------------------- */
+int chore_scene_layers_fwd(chore_handle* h,
+    const float* tri, const float* textures, const float* light, const float* face_opacity, int B, int F, int ts,
+    const float* pts, const float* point_rgb, const float* radius, float radius_px, int N, float point_depth_bias,
+    int size, int ssaa, float ambient, float near_z, float far_z, float tex_eps, const float* background3,
+    const int* face_group, int face_layers,
     float* rgb, float* depth, float* alpha, int* sample_id, void* workspace, chore_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------

@@ -5,6 +5,7 @@ Alternating in one process, device events, 5 warm-up rounds:
   B  chore_render_fwd, then chore_splat_fwd: the same passes without composition (two resolves, two sets of outputs)
   C  the layered composition tests/test_gpu_scene.py uses as its oracle: both calls at twice the size with ssaa = 1, then the select
      and the 2 x 2 pooling in torch (opaque faces: a select; the per-sample layers go through memory)
+  D  chore_scene_layers_fwd on A's inputs with the mesh index as face group, K = 2, 4 and 8 (reported as D over A)
     python scripts/scene_bench.py [calls] [--trace]     (--trace: a few calls of A at 2048 only, for rocprofv3 --kernel-trace --stats)"""
 import ctypes
 import os
@@ -31,7 +32,7 @@ NEAR, FAR, EPS, AMBIENT, BIAS, OPACITY = 0.1, 100.0, 1e-3, 0.6, 0.02, 0.6
 
 
 class Frame:
-    """the inputs of one image size and the three variants on buffers allocated up front"""
+    """the inputs of one image size and the variants on buffers allocated up front"""
 
     def __init__(self, S, dev):
         self.S, self.B, self.h = S, 1, _lib.handle(0)
@@ -52,6 +53,7 @@ class Frame:
         self.tri = vertices_to_faces(r.transform(verts), faces2).contiguous()
         self.F = self.tri.shape[1]
         self.op = torch.full((B, self.F), OPACITY, device=dev)
+        self.group = torch.cat((ru.mesh_face_group([ru.Mesh(v=bv, f=bf), ru.Mesh(v=sv, f=sf)], dev),) * 2, 1).contiguous()   # both windings
         self.bg = (ctypes.c_float * 3)(1.0, 1.0, 1.0)
         self.stream = torch.cuda.current_stream(dev).cuda_stream
         ws = lambda n: torch.empty(n, dtype=torch.uint8, device=dev)       # noqa: E731
@@ -60,7 +62,7 @@ class Frame:
         self.ws_render, self.ws_splat = ws(lib.chore_render_workspace_bytes(B, self.F, S, 2)), ws(lib.chore_splat_workspace_bytes(B, self.N, S, 2))
         self.ws_render1 = ws(lib.chore_render_workspace_bytes(B, self.F, 2 * S, 1))
         self.ws_splat1 = ws(lib.chore_splat_workspace_bytes(B, self.N, 2 * S, 1))
-        self.out_a, self.out_f, self.out_p = outs(S), outs(S), outs(S)
+        self.out_a, self.out_f, self.out_p, self.out_d = outs(S), outs(S), outs(S), outs(S)
         self.lay_f, self.lay_p = outs(2 * S), outs(2 * S)
         self.out_c = None
 
@@ -81,6 +83,14 @@ class Frame:
                                             self.col.data_ptr(), self.rad.data_ptr(), 0.0, self.N, BIAS, self.S, 2, AMBIENT, NEAR, FAR,
                                             EPS, self.bg, o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), None,
                                             self.ws_scene.data_ptr(), self.stream), self.h, "chore_scene_fwd")
+
+    def run_d(self, layers):
+        o = self.out_d
+        _lib.check(_lib.lib.chore_scene_layers_fwd(self.h, self.tri.data_ptr(), self.tex.data_ptr(), self.light.data_ptr(),
+                                                   self.op.data_ptr(), self.B, self.F, 4, self.ndc.data_ptr(), self.col.data_ptr(),
+                                                   self.rad.data_ptr(), 0.0, self.N, BIAS, self.S, 2, AMBIENT, NEAR, FAR, EPS, self.bg,
+                                                   self.group.data_ptr(), layers, o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(),
+                                                   None, self.ws_scene.data_ptr(), self.stream), self.h, "chore_scene_layers_fwd")
 
     def run_b(self):
         self._render(self.S, 2, self.out_f, self.ws_render)
@@ -125,12 +135,23 @@ def main():
             fr.run_a()
             fr.run_b()
             fr.run_c()
+            for k in (2, 4, 8):
+                fr.run_d(k)
         torch.cuda.synchronize()
-        ta, tb, tc = [], [], []
+        ta, tb, tc, td = [], [], [], {2: [], 4: [], 8: []}
         for _ in range(calls):
             ta.append(timed(fr.run_a))
             tb.append(timed(fr.run_b))
             tc.append(timed(fr.run_c))
+            for k in td:
+                td[k].append(timed(lambda: fr.run_d(k)))
+        fr.run_a()
+        fr.run_d(1)
+        torch.cuda.synchronize()
+        one_layer = [bool(torch.equal(a, d)) for a, d in zip(fr.out_a, fr.out_d)]
+        fr.run_d(8)
+        torch.cuda.synchronize()
+        seen = float((fr.out_a[0] != fr.out_d[0]).any(dim=1).float().mean())
         fr.run_a(opacity=False)          # opaque faces: what C composes
         torch.cuda.synchronize()
         same = [bool(torch.equal(a, c)) for a, c in zip(fr.out_a, fr.out_c)]
@@ -140,6 +161,11 @@ def main():
         print("A  chore_scene_fwd %4d px, 2x:                                    " % S + stats(ta))
         print("B  chore_render_fwd + chore_splat_fwd %4d px, 2x, not composed:   " % S + stats(tb))
         print("C  both at %4d px, 1x, torch select + avg_pool2d:                 " % (2 * S) + stats(tc))
+        for k in td:
+            print("D  chore_scene_layers_fwd %4d px, 2x, group = mesh, K = %d:         " % (S, k) + stats(td[k]) +
+                  "  D / A = %.3f" % (np.median(td[k]) / np.median(ta)))
+        print("D with K = 1 equals A bit for bit (rgb, depth, alpha): %s; share of the frame's pixels that K = 8 changes: %.4f"
+              % (one_layer, seen))
         spread_b = float(np.percentile(tb, 90) - np.percentile(tb, 10))
         print("median A - median B = %+.3f ms; B's own p10..p90 spread %.3f ms" % (np.median(ta) - np.median(tb), spread_b), flush=True)
 
