@@ -60,14 +60,7 @@ __device__ __forceinline__ void xform_x3_t(const u32x4& r0, const u32x4& r1, con
 #pragma unroll
         for (int j = 0; j < 8; ++j) t[j] *= mul;
     }
-    f16x8_t h, l;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        h[j] = (_Float16)t[j];
-        l[j] = (_Float16)(t[j] - (float)h[j]);
-    }
-    hi = __builtin_bit_cast(u32x4, h);
-    lo = __builtin_bit_cast(u32x4, l);
+    split8(t, hi, lo);
 }
 
 __device__ __forceinline__ void xform_x3(const u32x4& r0, const u32x4& r1, const float* sc, const float* sh, bool use_gn, u32x4& hi,
@@ -80,11 +73,7 @@ __device__ __forceinline__ void xform_x3(const u32x4& r0, const u32x4& r1, const
 }
 
 __device__ __forceinline__ void mfma_x3(f32x16& acc, const u32x4& ah, const u32x4& al, const u32x4& bh, const u32x4& bl) {
-    const f16x8_t a0 = __builtin_bit_cast(f16x8_t, ah), a1 = __builtin_bit_cast(f16x8_t, al);
-    const f16x8_t b0 = __builtin_bit_cast(f16x8_t, bh), b1 = __builtin_bit_cast(f16x8_t, bl);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0, acc, 0, 0, 0);   // small terms first
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0, acc, 0, 0, 0);
+    acc = mfma3(ah, al, bh, bl, acc);     // (enc_common.h: small terms first)
 }
 
 template <typename T>

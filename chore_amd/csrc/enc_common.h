@@ -123,6 +123,26 @@ __device__ __forceinline__ void x3_in_scale(const unsigned* cells, float& mul, f
     const unsigned e = ((unsigned)__builtin_amdgcn_readfirstlane((int)amax_read(cells)) >> 23) & 0xffu;       // biased exponent of max |x|
     if (e >= 14u && e <= 240u) { mul = __uint_as_float((267u - e) << 23); inv = __uint_as_float((e - 13u) << 23); }
 }
+// the fp16 x 3 arithmetic, one definition for the convolutions, the heads and the weight gradients: 8 fp32 values -> fp16 hi / lo
+// vectors, and acc += a b for two split operands as three fp16 MFMAs (the lo x lo term, 2^-22 relative, is dropped)
+typedef _Float16 x3_f16x8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ void split8(const float (&v)[8], u32x4& hi, u32x4& lo) {
+    x3_f16x8 h, l;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { h[j] = (_Float16)v[j]; l[j] = (_Float16)(v[j] - (float)h[j]); }
+    hi = __builtin_bit_cast(u32x4, h);
+    lo = __builtin_bit_cast(u32x4, l);
+}
+__device__ __forceinline__ f32x16 mfma3(const x3_f16x8& ah, const x3_f16x8& al, const x3_f16x8& bh, const x3_f16x8& bl, f32x16 acc) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc, 0, 0, 0);   // small terms first
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc, 0, 0, 0);
+    return acc;
+}
+__device__ __forceinline__ f32x16 mfma3(const u32x4& ah, const u32x4& al, const u32x4& bh, const u32x4& bl, f32x16 acc) {
+    return mfma3(__builtin_bit_cast(x3_f16x8, ah), __builtin_bit_cast(x3_f16x8, al), __builtin_bit_cast(x3_f16x8, bh),
+                 __builtin_bit_cast(x3_f16x8, bl), acc);
+}
 // block-wide max of the float bits `v` (non-negative floats compare like their bits) -> one atomic max into cells[cell]
 __device__ __forceinline__ void amax_block_atomic(unsigned v, unsigned* cells, int cell, unsigned* lds4 /*[nwaves]*/) {
 #pragma unroll

@@ -11,8 +11,6 @@
 #include "heads_f32.h"
 #include "enc_common.h"
 
-typedef _Float16 hf16x8_t __attribute__((ext_vector_type(8)));
-
 constexpr int QX_KS1 = 21;                                            // layer 1: 323 -> 336 = 21 k-steps of 16
 constexpr size_t QX_L1_VEC = (size_t)HEAD_NUM * QX_KS1 * 4 * 2 * 64;   // [head][ks][rb][plane][lane] u32x4
 constexpr size_t QX_L23_VEC = (size_t)HEAD_NUM * 2 * 4 * 2 * 4 * 2 * 64;   // [head][l][kb][s][rb][plane][lane]
@@ -29,21 +27,7 @@ constexpr size_t QX_TOTAL_VEC = QX_OFF_L1T + QX_L1T_VEC;
 constexpr size_t QX_ARENA_BYTES = QX_OFF_BYTES + QX_TOTAL_VEC * 16;
 constexpr float QX_SCALE = (float)(1 << X3_WSHIFT), QX_INV = 1.0f / (float)(1 << X3_WSHIFT);
 
-__device__ __forceinline__ void split8(const float (&v)[8], u32x4& hi, u32x4& lo) {
-    hf16x8_t h, l;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { h[j] = (_Float16)v[j]; l[j] = (_Float16)(v[j] - (float)h[j]); }
-    hi = __builtin_bit_cast(u32x4, h);
-    lo = __builtin_bit_cast(u32x4, l);
-}
-__device__ __forceinline__ f32x16 mfma3(const u32x4& ah, const u32x4& al, const u32x4& bh, const u32x4& bl, f32x16 acc) {
-    const hf16x8_t a0 = __builtin_bit_cast(hf16x8_t, ah), a1 = __builtin_bit_cast(hf16x8_t, al);
-    const hf16x8_t b0 = __builtin_bit_cast(hf16x8_t, bh), b1 = __builtin_bit_cast(hf16x8_t, bl);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b0, acc, 0, 0, 0);   // small terms first
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b1, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0, acc, 0, 0, 0);
-    return acc;
-}
+// (split8 and mfma3, the hi / lo split and the three-MFMA product, are enc_common.h's)
 __device__ __forceinline__ f32x16 scaled_bias(const float* arena, int head, int layer, int rb, int half) {
     f32x16 b = load_bias_frag(arena, head, layer, rb, half);
 #pragma unroll

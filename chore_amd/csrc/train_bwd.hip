@@ -9,9 +9,17 @@
 //             fragments come from the same row-major images through ds_read_b64_tr_b16 (in a 16-lane group lane i
 //             addresses 4 contiguous elements of row i>>2, column chunk i&3 of a 4x16 block and receives column i;
 //             measured with scripts/probes/tr_probe.hip), two reads per fragment, no software transpose.
-//     A workgroup owns 32 output x 32 input channels (all taps) and walks a share of the 8x32-pixel tiles; its four
-//     waves split the tile rows and reduce through LDS in a fixed order at the end; the per-share partials are
-//     summed in order by a second kernel: no float atomics, bit-reproducible.
+//     Five kernels: wgrad_kernel (32 x 32 channels per workgroup, fp32 and bf16), wgrad64_kernel (bf16, 64 x 64), and for the
+//     fp16 x 3 mode wgrad64_x3_kernel, wgrad64_x3_pc_kernel (specialised waves) and wgrad128_x3_pc_kernel (1x1, 128 x 128).  A
+//     workgroup owns a channel tile pair (all taps) and walks a share of the pixel tiles; the per-share partials are summed in
+//     order by a second kernel: no float atomics, bit-reproducible.
+//     What the kernels have in common is written once: the LDS layouts (W32Lds ... W128Lds, read by the kernels AND by the
+//     host), the block -> (share, pair) mapping (wgrad_share_pair, chosen by wgrad_xcd_mapping on both sides), the
+//     transposing fragment read (tr_frag), the tile decode (tile_origin), the hi / lo plane stores (x3_store), the bf16
+//     GroupNorm + ReLU repack and the producers' dbias sum; the hi / lo split and the three-MFMA product are enc_common.h's.
+//     A helper was taken where the kernel compiles to the same instructions with it; what stayed inline and why: DESIGN.md §4.
+//     On the host wgrad_plan() is the one place that decides kernel, tiling, shares, partial layout, grid and LDS bytes of a
+//     layer; the launcher, the workspace query and chore_gemm_tn_f32 read it.
 //   * GroupNorm+ReLU backward: one streaming pass accumulates, exactly (the integer accumulators of
 //     enc_common.h), dgamma/dbeta per channel and the two per-(image, group) sums the input gradient needs; a
 //     second pass writes dx = rstd * (g*gamma - mean(g*gamma) - xhat * mean(g*gamma*xhat)), g = dA * [y > 0].
@@ -21,9 +29,12 @@ typedef __bf16 tb_bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
-constexpr int TH = 8, TW = 32;                 // pixel tile
-constexpr int PW = TW + 2, PH = TH + 2;        // halo tile of the 3x3 case
-constexpr int CT32 = 32;                       // channels per operand tile
+constexpr int TW = 32;                         // pixels per tile row, every kernel
+constexpr int TH = 8, WX_TH = 4, WP_TH = 2;    // tile rows: wgrad_kernel and wgrad64_kernel / wgrad64_x3_kernel / wgrad64_x3_pc_kernel
+constexpr int CT32 = 32;                       // channels per operand tile of wgrad_kernel
+constexpr int W64_N = 64 * 64;                  // floats of one tap of a 64 x 64-channel partial
+constexpr int W64_PITCH = 160;                 // bytes per pixel row of the 64-channel LDS images (64 x 16 bit = 128 + 32 pad)
+constexpr int W128_PITCH = 320, W128_PX = 32;  // wgrad128_x3_pc_kernel: row pitch, pixels per tile
 
 template <typename T> __device__ __forceinline__ float ld1(const T* p);
 template <> __device__ __forceinline__ float ld1<float>(const float* p) { return *p; }
@@ -43,7 +54,7 @@ struct WgradArgs {
     int B, H, W, Cin, Cout;
     int xs, ys;               // row strides (elements) of x and dy: Cin / Cout for dense NHWC tensors
     long long npix;           // pixels that exist (B*H*W, or fewer when a row list is walked as a ragged image)
-    float* part;              // [S][Cout/32][Cin/32][TAPS][32][32] partial sums
+    float* part;              // [S][Cout/ct][Cin/ct][TAPS][ct][ct] partial sums
     float* part_bias;         // [S][Cout] or null
     int S;                    // shares of the pixel tiles
     const unsigned* dy_amax;  // fp16 x 3 kernels: AMAX_CELLS partial maxima of |dy| (enc_common.h), or null
@@ -55,15 +66,152 @@ struct WgradArgs {
 #define WGRAD_DBG 0
 #endif
 
+// ---- LDS layouts: each stated once, read by its kernel and by wgrad_plan (byte offsets into the dynamic LDS) ----
+// a ROWS x TW pixel tile and, at 3 x 3, its halo: the rows of the two images, and the 8-channel units per thread when 256 threads
+// stage them
+template <int TAPS, int ROWS> struct WTile {
+    static constexpr int PAD = TAPS == 9 ? 1 : 0;
+    static constexpr int AW = TW + 2 * PAD, AH = ROWS + 2 * PAD, AROWS = AH * AW, YROWS = ROWS * TW;
+    static constexpr int NVX = (AROWS * 8 + 255) / 256, NVY = YROWS * 8 / 256;
+};
+template <typename T, int TAPS> struct W32Lds : WTile<TAPS, TH> {         // wgrad_kernel: [AROWS][32] input, [256][32] dY, [32][2] scale/shift
+    static constexpr int A = 0, Y = WTile<TAPS, TH>::AROWS * CT32 * (int)sizeof(T), SS = Y + TH * TW * CT32 * (int)sizeof(T);
+    static constexpr int RED = 4 * CT32 * CT32 * (int)sizeof(float);          // [4 waves][32][32], after the loop, over the images
+    static constexpr int BYTES = SS + 256 > RED ? SS + 256 : RED;
+};
+template <int TAPS> struct W64Lds : WTile<TAPS, TH> {                     // wgrad64_kernel: one bf16 plane per image, [64][2] scale/shift
+    static constexpr int A = 0, Y = WTile<TAPS, TH>::AROWS * W64_PITCH, SS = Y + TH * TW * W64_PITCH;
+    static constexpr int BYTES = SS + 64 * 2 * (int)sizeof(float);
+};
+template <int TAPS> struct W64X3Lds : WTile<TAPS, WX_TH> {                // wgrad64_x3_kernel: hi and lo plane per image, [64][2] scale/shift
+    static constexpr int PLA = WTile<TAPS, WX_TH>::AROWS * W64_PITCH, PLY = WX_TH * TW * W64_PITCH;     // bytes of one plane
+    static constexpr int A = 0, Y = 2 * PLA, SS = Y + 2 * PLY;
+    static constexpr int BYTES = SS + 64 * 2 * (int)sizeof(float);
+};
+template <int TAPS> struct W64PcLds : WTile<TAPS, WP_TH> {                // wgrad64_x3_pc_kernel: two buffers of A hi, A lo, Y hi, Y lo
+    static constexpr int PLA = WTile<TAPS, WP_TH>::AROWS * W64_PITCH, PLY = WP_TH * TW * W64_PITCH;
+    static constexpr int A = 0, Y = 2 * PLA, BUF = Y + 2 * PLY;
+    static constexpr int BYTES = 2 * BUF;
+};
+struct W128Lds {                                                           // wgrad128_x3_pc_kernel: the same with [32 pixels][128 ch] planes
+    static constexpr int PL = W128_PX * W128_PITCH;
+    static constexpr int A = 0, Y = 2 * PL, BUF = Y + 2 * PL;
+    static constexpr int BYTES = 2 * BUF;
+};
+
+// ---- the blocks the kernels share ----
+// how the 64- and 128-channel kernels number their workgroups, from the share count alone: the kernels map with it and the
+// launcher's witness flag (WGRAD_FLAG_XCD) reports it
+__host__ __device__ inline bool wgrad_xcd_mapping(int S) { return S % 8 == 0; }
+
+// workgroup -> (share of the pixel tiles, channel tile pair).  Workgroups that share pixel tiles (same share, different pair) are
+// placed on one XCD (id % 8) where the shares divide over the eight, so that the second and later readers of a tile hit that XCD's L2
+__device__ __forceinline__ void wgrad_share_pair(int S, int npairs, int& share, int& pair) {
+    const int L = blockIdx.x;
+    if (wgrad_xcd_mapping(S)) { const int xcd = L & 7, j = L >> 3; share = (j / npairs) * 8 + xcd; pair = j % npairs; }
+    else { share = L / npairs; pair = L % npairs; }
+}
+
+// pixel tile `tile` of a (B, H, W) map cut into ROWS x TW tiles: its image and origin
+template <int ROWS>
+__device__ __forceinline__ void tile_origin(int tile, int tiles_x, int tiles_y, int& b, int& ty0, int& tx0) {
+    const int tt = tile % (tiles_x * tiles_y);
+    b = tile / (tiles_x * tiles_y);
+    ty0 = (tt / tiles_x) * ROWS;
+    tx0 = (tt % tiles_x) * TW;
+}
+
+// GroupNorm + ReLU on 8 bf16 channels c0 .. c0 + 7 with the scale / shift pairs of the interleaved [channel][2] LDS table: the
+// arithmetic of conv_detail::xform<bf16_t>, which these kernels do not call -- it converts pair by pair, and the instruction order
+// that gives differs from the one the two bf16 kernels were measured with (all unpacks, all FMAs, all packs)
+__device__ __forceinline__ u32x4 gn_relu_bf16x8(u32x4 val, const float* ss, int c0) {
+    float f[8];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { f[2 * j] = __uint_as_float(val[j] << 16); f[2 * j + 1] = __uint_as_float(val[j] & 0xffff0000u); }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { const float t = fmaf(f[j], ss[2 * (c0 + j)], ss[2 * (c0 + j) + 1]); f[j] = t > 0.f ? t : 0.f; }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) val[j] = pack2bf(f[2 * j], f[2 * j + 1]);
+    return val;
+}
+
+// Transposing fragment read from a [pixel][channel] image of 16-bit elements with PITCH bytes per pixel: p = image + pixel * PITCH +
+// channel * 2 + the lane's offset (its row of the 4-row block and 4-column chunk: `lane_off` of the kernels); 8 consecutive pixels of
+// this lane's channel from two reads (pixels +0..3 and +4..7 of its k half)
+typedef short tb_s16x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) tb_s16x4 lds_s16x4;
+template <typename FR, int PITCH>
+__device__ __forceinline__ FR tr_frag(const char* p) {
+    const tb_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p);
+    const tb_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 4 * PITCH));
+    typedef short s16x8 __attribute__((ext_vector_type(8)));
+    const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return __builtin_bit_cast(FR, v);
+}
+
+// Three taps of one kernel row from ONE set of transposing reads (fp16 / bf16 weight gradients, 3x3): the fragments of taps kx = 0, 1, 2
+// are 8-pixel windows starting at pixels 0, 1, 2 of the same channel -- 10 of 12 pixels shared.  Three ds_read_b64_tr_b16 (pixels 0-3,
+// 4-7, 8-11 of this lane's k half) give six dwords; window 0 = dwords 0-3, window 2 = dwords 1-4, window 1 = four 16-bit funnel
+// shifts.  6 reads instead of 3 x 4 per (kernel row, plane).  Used by wgrad64_x3_kernel (150 -> 141 us on the largest layer, 1 - 4 us on
+// the others); NOT by wgrad64_x3_pc_kernel, where it measured slower.
+struct TrWin { unsigned d[6]; };
+__device__ __forceinline__ TrWin tr_load3(const char* p) {
+    const tb_s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p);
+    const tb_s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 4 * W64_PITCH));
+    const tb_s16x4 c = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 8 * W64_PITCH));
+    typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
+    const u32x2_t ua = __builtin_bit_cast(u32x2_t, a), ub = __builtin_bit_cast(u32x2_t, b), uc = __builtin_bit_cast(u32x2_t, c);
+    TrWin w;
+    w.d[0] = ua[0]; w.d[1] = ua[1]; w.d[2] = ub[0]; w.d[3] = ub[1]; w.d[4] = uc[0]; w.d[5] = uc[1];
+    return w;
+}
+template <typename FR>
+__device__ __forceinline__ FR tr_window(const TrWin& w, int kx) {
+    u32x4 v;
+    if (kx == 0) v = u32x4{w.d[0], w.d[1], w.d[2], w.d[3]};
+    else if (kx == 2) v = u32x4{w.d[1], w.d[2], w.d[3], w.d[4]};
+    else v = u32x4{__builtin_amdgcn_alignbit(w.d[1], w.d[0], 16), __builtin_amdgcn_alignbit(w.d[2], w.d[1], 16),
+                   __builtin_amdgcn_alignbit(w.d[3], w.d[2], 16), __builtin_amdgcn_alignbit(w.d[4], w.d[3], 16)};
+    return __builtin_bit_cast(FR, v);
+}
+
+// one staged unit (8 channels of pixel `row`) into the hi and the lo plane of an image, `plane` bytes apart
+template <int PITCH>
+__device__ __forceinline__ void x3_store(char* img, int plane, int row, int v, const u32x4& hi, const u32x4& lo) {
+    *(u32x4*)(img + row * PITCH + v * 16) = hi;
+    *(u32x4*)(img + plane + row * PITCH + v * 16) = lo;
+}
+
+// LDS traffic of this wave done, then the workgroup barrier; vector-memory loads stay in flight across it (__syncthreads() would
+// wait for the producers' prefetched global loads at every tile).  The specialised-wave kernels hand their buffers over with it.
+__device__ __forceinline__ void wp_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+// dbias partial of this share in the specialised-wave kernels (a pixel row = SLOTS 8-channel slots): every producer thread has left
+// the sums of its slot in red[ptid][8]; channel tid < 8 SLOTS adds its 256 / SLOTS threads in thread order
+template <int SLOTS>
+__device__ __forceinline__ void pc_dbias(const WgradArgs& a, const float* red, int share, int co0, float yinv, int tid) {
+    float sum = 0.f;
+    const int vv = tid >> 3, j = tid & 7;              // channel tid = slot vv, element j
+    for (int p = 0; p < 256 / SLOTS; ++p) sum += red[(p * SLOTS + vv) * 8 + j];
+    a.part_bias[(size_t)share * a.Cout + co0 + tid] = sum * yinv;
+}
+
+// ------------------------------------------------------------------------------------------------
+// 32 x 32 channels per workgroup, fp32 and bf16 (every layer in fp32; below 64 channels in the other modes).  The four waves split
+// the rows of an 8 x 32-pixel tile and reduce through LDS in a fixed order at the end.
+// ------------------------------------------------------------------------------------------------
 template <typename T, int TAPS>
 __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs a) {
-    constexpr int PAD = TAPS == 9 ? 1 : 0;
-    constexpr int AW = TW + 2 * PAD, AH = TH + 2 * PAD, AROWS = AH * AW;
+    using L = W32Lds<T, TAPS>;
+    constexpr int PAD = L::PAD, AW = L::AW, AROWS = L::AROWS;
     constexpr int ES = sizeof(T);
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    T* imgA = (T*)smem;                                   // [AROWS][32]  relu(gn(x)) halo tile, zero outside the image
-    T* imgY = (T*)(smem + AROWS * CT32 * ES);             // [256][32]    dY tile
-    float* ss = (float*)(smem + (AROWS + TH * TW) * CT32 * ES);   // [32][2] scale/shift of this image's channels
+    T* imgA = (T*)(smem + L::A);                          // [AROWS][32]  relu(gn(x)) halo tile, zero outside the image
+    T* imgY = (T*)(smem + L::Y);                          // [256][32]    dY tile
+    float* ss = (float*)(smem + L::SS);                   // [32][2] scale/shift of this image's channels
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int co0 = blockIdx.x * CT32, ci0 = blockIdx.y * CT32, share = blockIdx.z;
     const int tiles_x = (a.W + TW - 1) / TW, tiles_y = (a.H + TH - 1) / TH;
@@ -81,8 +229,8 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs a) {
     int cur_b = -1;
 
     for (int tile = share; tile < tiles; tile += a.S) {
-        const int b = tile / (tiles_x * tiles_y), tt = tile % (tiles_x * tiles_y);
-        const int ty0 = (tt / tiles_x) * TH, tx0 = (tt % tiles_x) * TW;
+        int b, ty0, tx0;
+        tile_origin<TH>(tile, tiles_x, tiles_y, b, ty0, tx0);
         __syncthreads();                                  // previous tile fully consumed
         if (use_gn && b != cur_b) {
             if (tid < CT32) gn_scale_shift(a.st, a.B, b, a.Cin, ci0 + tid, a.H * a.W, a.gamma, a.beta, ss[2 * tid], ss[2 * tid + 1]);
@@ -97,21 +245,13 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs a) {
             u32x4 val = {0u, 0u, 0u, 0u};
             if (y >= 0 && y < a.H && x >= 0 && x < a.W && ((long long)b * a.H + y) * a.W + x < a.npix) {
                 val = *(const u32x4*)(X + (((size_t)b * a.H + y) * a.W + x) * a.xs + ci0 + v * VE);
-                if (use_gn) {
-                    float f[8];
-                    if constexpr (ES == 2) {
+                if constexpr (ES == 2) {
+                    if (use_gn) val = gn_relu_bf16x8(val, ss, v * 8);
+                } else if (use_gn) {
 #pragma unroll
-                        for (int j = 0; j < 4; ++j) { f[2 * j] = __uint_as_float(val[j] << 16); f[2 * j + 1] = __uint_as_float(val[j] & 0xffff0000u); }
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) { const float t = fmaf(f[j], ss[2 * (v * 8 + j)], ss[2 * (v * 8 + j) + 1]); f[j] = t > 0.f ? t : 0.f; }
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) val[j] = pack2bf(f[2 * j], f[2 * j + 1]);
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const float t = fmaf(__uint_as_float(val[j]), ss[2 * (v * 4 + j)], ss[2 * (v * 4 + j) + 1]);
-                            val[j] = __float_as_uint(t > 0.f ? t : 0.f);
-                        }
+                    for (int j = 0; j < 4; ++j) {
+                        const float t = fmaf(__uint_as_float(val[j]), ss[2 * (v * 4 + j)], ss[2 * (v * 4 + j) + 1]);
+                        val[j] = __float_as_uint(t > 0.f ? t : 0.f);
                     }
                 }
             }
@@ -150,7 +290,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs a) {
             // transposing reads: lane -> (row within the 4-row block, 4-column chunk) of its 16-lane group
             const int i16 = lane & 15, g = (lane >> 4) & 1, h = lane >> 5;
             const int rsel = i16 >> 2, csel = (i16 & 3) * 4 + g * 16;
-            auto frag = [&](const T* img, int row0) -> tb_bf16x8 {      // rows row0 + 8h + {0..3} and {4..7}
+            auto frag = [&](const T* img, int row0) -> tb_bf16x8 {       // rows row0 + 8h + {0..3} and {4..7}
                 unsigned long long lo, hi;
                 const unsigned a0 = (unsigned)(size_t)(img + (row0 + 8 * h + rsel) * CT32 + csel);
                 asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo) : "v"(a0));
@@ -180,16 +320,17 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs a) {
     }
     // ---- reduce the four waves (fixed order) and write this share's partial ----
     __syncthreads();
-    float* red = (float*)smem;                            // [4][32][32] one tap at a time
+    constexpr int N = CT32 * CT32;
+    float* red = (float*)smem;                            // [4][32][32] one tap at a time (L::RED bytes)
     const int half = lane >> 5, col = lane & 31;
-    float* out = a.part + ((((size_t)share * gridDim.x + blockIdx.x) * gridDim.y + blockIdx.y) * TAPS) * 1024;
+    float* out = a.part + ((((size_t)share * gridDim.x + blockIdx.x) * gridDim.y + blockIdx.y) * TAPS) * N;
 #pragma unroll 1
     for (int t = 0; t < TAPS; ++t) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) red[(wid * 32 + mfma32_row(r, half)) * 32 + col] = acc[t][r];
         __syncthreads();
-        for (int i = tid; i < 1024; i += 256)
-            out[(size_t)t * 1024 + i] = ((red[i] + red[1024 + i]) + red[2048 + i]) + red[3072 + i];
+        for (int i = tid; i < N; i += 256)
+            out[(size_t)t * N + i] = ((red[i] + red[N + i]) + red[2 * N + i]) + red[3 * N + i];
         __syncthreads();
     }
     if (a.part_bias && blockIdx.y == 0 && tid < CT32) a.part_bias[(size_t)share * a.Cout + co0 + tid] = bias_acc;
@@ -205,57 +346,19 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs a) {
 // ~5.1k LDS cycles against 4.6k MFMA cycles per tile).  LDS images are [pixel][64 ch] with a 160-byte pitch: the
 // four 4x16 blocks a transposing read touches fall into disjoint banks.  Staging issues all vector loads of a
 // tensor before the first use.
-// Workgroups that share pixel tiles (same share, different channel pair) are placed on one XCD (id % 8) so the
-// second and later readers of a tile hit that XCD's L2.
 // ------------------------------------------------------------------------------------------------
-constexpr int W64_PITCH = 160;                 // bytes per pixel row of the LDS images (64 bf16 = 128 + 32 pad)
-typedef short tb_s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) tb_s16x4 lds_s16x4;
-
-// Three taps of one kernel row from ONE set of transposing reads (fp16 / bf16 weight gradients, 3x3): the fragments of taps kx = 0, 1, 2
-// are 8-pixel windows starting at pixels 0, 1, 2 of the same channel -- 10 of 12 pixels shared.  Three ds_read_b64_tr_b16 (pixels 0-3,
-// 4-7, 8-11 of this lane's k half) give six dwords; window 0 = dwords 0-3, window 2 = dwords 1-4, window 1 = four 16-bit funnel
-// shifts.  6 reads instead of 3 x 4 per (kernel row, plane).  Used by wgrad64_x3_kernel (150 -> 141 us on the largest layer, 1 - 4 us on
-// the others); NOT by wgrad64_x3_pc_kernel, where it measured slower.
-struct TrWin { unsigned d[6]; };
-__device__ __forceinline__ TrWin tr_load3(const char* p) {
-    const tb_s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p);
-    const tb_s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 4 * W64_PITCH));
-    const tb_s16x4 c = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 8 * W64_PITCH));
-    typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-    const u32x2_t ua = __builtin_bit_cast(u32x2_t, a), ub = __builtin_bit_cast(u32x2_t, b), uc = __builtin_bit_cast(u32x2_t, c);
-    TrWin w;
-    w.d[0] = ua[0]; w.d[1] = ua[1]; w.d[2] = ub[0]; w.d[3] = ub[1]; w.d[4] = uc[0]; w.d[5] = uc[1];
-    return w;
-}
-template <typename FR>
-__device__ __forceinline__ FR tr_window(const TrWin& w, int kx) {
-    u32x4 v;
-    if (kx == 0) v = u32x4{w.d[0], w.d[1], w.d[2], w.d[3]};
-    else if (kx == 2) v = u32x4{w.d[1], w.d[2], w.d[3], w.d[4]};
-    else v = u32x4{__builtin_amdgcn_alignbit(w.d[1], w.d[0], 16), __builtin_amdgcn_alignbit(w.d[2], w.d[1], 16),
-                   __builtin_amdgcn_alignbit(w.d[3], w.d[2], 16), __builtin_amdgcn_alignbit(w.d[4], w.d[3], 16)};
-    return __builtin_bit_cast(FR, v);
-}
-
-
 template <int TAPS>
 __global__ __launch_bounds__(256) void wgrad64_kernel(WgradArgs a) {
-    constexpr int PAD = TAPS == 9 ? 1 : 0;
-    constexpr int AW = TW + 2 * PAD, AH = TH + 2 * PAD, AROWS = AH * AW;
-    constexpr int NVX = (AROWS * 8 + 255) / 256, NVY = TH * TW * 8 / 256;      // 16-byte vectors per thread
+    using L = W64Lds<TAPS>;
+    constexpr int PAD = L::PAD, AW = L::AW, AROWS = L::AROWS, NVX = L::NVX, NVY = L::NVY;      // NV*: 16-byte vectors per thread
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* imgA = smem;                                     // [AROWS] x 160 B
-    char* imgY = smem + AROWS * W64_PITCH;                 // [256] x 160 B
-    float* ss = (float*)(imgY + TH * TW * W64_PITCH);      // [64][2]
+    char* imgA = smem + L::A;                              // [AROWS] x 160 B
+    char* imgY = smem + L::Y;                              // [256] x 160 B
+    float* ss = (float*)(smem + L::SS);                    // [64][2]
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, cih = wid & 1, coh = wid >> 1;
     const int nbo = a.Cout / 64, nbc = a.Cin / 64, npairs = nbo * nbc;
     int share, pair;
-    {
-        const int L = blockIdx.x;
-        if (a.S % 8 == 0) { const int xcd = L & 7, j = L >> 3; share = (j / npairs) * 8 + xcd; pair = j % npairs; }
-        else { share = L / npairs; pair = L % npairs; }
-    }
+    wgrad_share_pair(a.S, npairs, share, pair);
     const int co0 = (pair / nbc) * 64, ci0 = (pair % nbc) * 64;
     const int tiles_x = (a.W + TW - 1) / TW, tiles_y = (a.H + TH - 1) / TH;
     const int tiles = a.B * tiles_x * tiles_y;
@@ -272,17 +375,10 @@ __global__ __launch_bounds__(256) void wgrad64_kernel(WgradArgs a) {
     int cur_b = -1;
     const int h = lane >> 5, g = (lane >> 4) & 1, i16 = lane & 15;
     const int lane_off = (8 * h + (i16 >> 2)) * W64_PITCH + (g * 16 + (i16 & 3) * 4) * 2;
-    auto frag = [&](const char* p) -> tb_bf16x8 {          // p: image + pixel * pitch + channel * 2 (+ lane_off)
-        const tb_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p);
-        const tb_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 4 * W64_PITCH));
-        typedef short s16x8 __attribute__((ext_vector_type(8)));
-        const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        return __builtin_bit_cast(tb_bf16x8, v);
-    };
 
     for (int tile = share; tile < tiles; tile += a.S) {
-        const int b = tile / (tiles_x * tiles_y), tt = tile % (tiles_x * tiles_y);
-        const int ty0 = (tt / tiles_x) * TH, tx0 = (tt % tiles_x) * TW;
+        int b, ty0, tx0;
+        tile_origin<TH>(tile, tiles_x, tiles_y, b, ty0, tx0);
         __syncthreads();                                   // previous tile fully consumed
         if (use_gn && b != cur_b) {
             if (tid < 64) gn_scale_shift(a.st, a.B, b, a.Cin, ci0 + tid, a.H * a.W, a.gamma, a.beta, ss[2 * tid], ss[2 * tid + 1]);
@@ -318,15 +414,7 @@ __global__ __launch_bounds__(256) void wgrad64_kernel(WgradArgs a) {
                 const int i = tid + 256 * q, row = i >> 3, v = i & 7;
                 const int y = ty0 + row / AW - PAD, x = tx0 + row % AW - PAD;
                 u32x4 val = vx[q];
-                if (use_gn) {
-                    float f[8];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { f[2 * j] = __uint_as_float(val[j] << 16); f[2 * j + 1] = __uint_as_float(val[j] & 0xffff0000u); }
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) { const float t = fmaf(f[j], ss[2 * (v * 8 + j)], ss[2 * (v * 8 + j) + 1]); f[j] = t > 0.f ? t : 0.f; }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) val[j] = pack2bf(f[2 * j], f[2 * j + 1]);
-                }
+                if (use_gn) val = gn_relu_bf16x8(val, ss, v * 8);
                 if (y < 0 || y >= a.H || x < 0 || x >= a.W) { val[0] = 0u; val[1] = 0u; val[2] = 0u; val[3] = 0u; }
                 if (i < AROWS * 8) *(u32x4*)(imgA + row * W64_PITCH + v * 16) = val;
             }
@@ -342,7 +430,7 @@ __global__ __launch_bounds__(256) void wgrad64_kernel(WgradArgs a) {
         for (int y = 0; y < TH; ++y) {
 #pragma unroll
             for (int xb = 0; xb < TW; xb += 16) {
-                const tb_bf16x8 fy = frag(baseY + (y * TW + xb) * W64_PITCH);
+                const tb_bf16x8 fy = tr_frag<tb_bf16x8, W64_PITCH>(baseY + (y * TW + xb) * W64_PITCH);
                 if constexpr (TAPS == 9) {      // the three taps of a kernel row from one set of reads (tr_load3)
 #pragma unroll
                     for (int ky = 0; ky < 3; ++ky) {
@@ -352,25 +440,22 @@ __global__ __launch_bounds__(256) void wgrad64_kernel(WgradArgs a) {
                             acc[ky * 3 + kx] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fy, tr_window<tb_bf16x8>(w, kx), acc[ky * 3 + kx], 0, 0, 0);
                     }
                 } else {
-                    const tb_bf16x8 fx = frag(baseA + (y * AW + xb) * W64_PITCH);
+                    const tb_bf16x8 fx = tr_frag<tb_bf16x8, W64_PITCH>(baseA + (y * AW + xb) * W64_PITCH);
                     acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fy, fx, acc[0], 0, 0, 0);
                 }
             }
         }
     }
-    // ---- this share's partial: [tap][64 co][64 ci] ----
     const int col = lane & 31;
-    float* out = a.part + ((size_t)share * npairs + pair) * TAPS * 4096;
+    float* out = a.part + ((size_t)share * npairs + pair) * TAPS * W64_N;
 #pragma unroll
     for (int t = 0; t < TAPS; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-            out[(size_t)t * 4096 + (coh * 32 + mfma32_row(r, h)) * 64 + cih * 32 + col] = acc[t][r];
+            out[(size_t)t * W64_N + (coh * 32 + mfma32_row(r, h)) * 64 + cih * 32 + col] = acc[t][r];
     if (a.part_bias && pair % nbc == 0 && tid < 64) a.part_bias[(size_t)share * a.Cout + co0 + tid] = bias_acc;
 }
 
-
-typedef _Float16 tb_f16x8 __attribute__((ext_vector_type(8)));
 // ------------------------------------------------------------------------------------------------
 // fp16 x 3 weight gradient (CHORE_F16X3 training: fp32 tensors, fp32-grade result on the fp16 matrix cores).
 // The structure of wgrad64_kernel -- 64 output x 64 input channels x all taps per workgroup, wave (coh, cih) owns a 32 x 32
@@ -382,27 +467,20 @@ typedef _Float16 tb_f16x8 __attribute__((ext_vector_type(8)));
 // the power of two that puts max |dY| (WgradArgs::dy_amax, from the kernel that produced dY) at 2^13 .. 2^14 before the split --
 // an fp16 pair keeps 22 bits only above 2^-3 -- and the accumulators by its inverse at the end.
 // ------------------------------------------------------------------------------------------------
-constexpr int WX_TH = 4;
-
 template <int TAPS>
 __global__ __launch_bounds__(256) void wgrad64_x3_kernel(WgradArgs a) {
     f16_saturate_mode();
-    constexpr int PAD = TAPS == 9 ? 1 : 0;
-    constexpr int AW = TW + 2 * PAD, AH = WX_TH + 2 * PAD, AROWS = AH * AW, YROWS = WX_TH * TW;
-    constexpr int NVX = (AROWS * 8 + 255) / 256, NVY = YROWS * 8 / 256;        // 8-channel slots (two 16-byte loads) per thread
-    constexpr int PLA = AROWS * W64_PITCH, PLY = YROWS * W64_PITCH;            // bytes of one plane
+    using L = W64X3Lds<TAPS>;
+    constexpr int PAD = L::PAD, AW = L::AW, AROWS = L::AROWS, YROWS = L::YROWS, PLA = L::PLA, PLY = L::PLY;
+    constexpr int NVX = L::NVX, NVY = L::NVY;              // 8-channel slots (two 16-byte loads) per thread
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* imgA = smem;                                     // [2 planes][AROWS] x 160 B
-    char* imgY = smem + 2 * PLA;                           // [2 planes][YROWS] x 160 B
-    float* ss = (float*)(imgY + 2 * PLY);                  // [64][2]
+    char* imgA = smem + L::A;                              // [2 planes][AROWS] x 160 B
+    char* imgY = smem + L::Y;                              // [2 planes][YROWS] x 160 B
+    float* ss = (float*)(smem + L::SS);                    // [64][2]
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, cih = wid & 1, coh = wid >> 1;
     const int nbo = a.Cout / 64, nbc = a.Cin / 64, npairs = nbo * nbc;
     int share, pair;
-    {
-        const int L = blockIdx.x;
-        if (a.S % 8 == 0) { const int xcd = L & 7, j = L >> 3; share = (j / npairs) * 8 + xcd; pair = j % npairs; }
-        else { share = L / npairs; pair = L % npairs; }
-    }
+    wgrad_share_pair(a.S, npairs, share, pair);
     const int co0 = (pair / nbc) * 64, ci0 = (pair % nbc) * 64;
     const int tiles_x = (a.W + TW - 1) / TW, tiles_y = (a.H + WX_TH - 1) / WX_TH;
     const int tiles = a.B * tiles_x * tiles_y;
@@ -421,21 +499,6 @@ __global__ __launch_bounds__(256) void wgrad64_x3_kernel(WgradArgs a) {
     int cur_b = -1;
     const int h = lane >> 5, g = (lane >> 4) & 1, i16 = lane & 15;
     const int lane_off = (8 * h + (i16 >> 2)) * W64_PITCH + (g * 16 + (i16 & 3) * 4) * 2;
-    auto frag = [&](const char* p) -> tb_f16x8 {           // p: plane + pixel * pitch + channel * 2 (+ lane_off)
-        const tb_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p);
-        const tb_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 4 * W64_PITCH));
-        typedef short s16x8 __attribute__((ext_vector_type(8)));
-        const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        return __builtin_bit_cast(tb_f16x8, v);
-    };
-    // 8 fp32 values -> fp16 hi / lo vectors
-    auto split8 = [](const float (&f)[8], u32x4& hi, u32x4& lo) {
-        tb_f16x8 hh, ll;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { hh[j] = (_Float16)f[j]; ll[j] = (_Float16)(f[j] - (float)hh[j]); }
-        hi = __builtin_bit_cast(u32x4, hh);
-        lo = __builtin_bit_cast(u32x4, ll);
-    };
 
     // The global loads of tile i + 1 are issued BEFORE the MFMAs of tile i and consumed after them (registers vy / vx live across
     // the MFMA loop): with one wave per SIMD nothing else hides a load's round trip, and the first version -- load, wait, split,
@@ -443,8 +506,8 @@ __global__ __launch_bounds__(256) void wgrad64_x3_kernel(WgradArgs a) {
     // unconditional at clamped addresses (a branch around a load makes the compiler wait for everything in flight).
     u32x4 vy[NVY][2], vx[NVX][2];
     auto issue_loads = [&](int tile) {
-        const int b = tile / (tiles_x * tiles_y), tt = tile % (tiles_x * tiles_y);
-        const int ty0 = (tt / tiles_x) * WX_TH, tx0 = (tt % tiles_x) * TW;
+        int b, ty0, tx0;
+        tile_origin<WX_TH>(tile, tiles_x, tiles_y, b, ty0, tx0);
 #pragma unroll
         for (int q = 0; q < NVY; ++q) {
             const int i = tid + 256 * q, row = i >> 3, v = i & 7;
@@ -462,8 +525,8 @@ __global__ __launch_bounds__(256) void wgrad64_x3_kernel(WgradArgs a) {
     };
     if (share < tiles && !(WGRAD_DBG & 4)) issue_loads(share);
     for (int tile = share; tile < tiles; tile += a.S) {
-        const int b = tile / (tiles_x * tiles_y), tt = tile % (tiles_x * tiles_y);
-        const int ty0 = (tt / tiles_x) * WX_TH, tx0 = (tt % tiles_x) * TW;
+        int b, ty0, tx0;
+        tile_origin<WX_TH>(tile, tiles_x, tiles_y, b, ty0, tx0);
         __syncthreads();                                   // previous tile fully consumed
         if (use_gn && b != cur_b) {
             if (tid < 64) gn_scale_shift(a.st, a.B, b, a.Cin, ci0 + tid, a.H * a.W, a.gamma, a.beta, ss[2 * tid], ss[2 * tid + 1]);
@@ -480,8 +543,7 @@ __global__ __launch_bounds__(256) void wgrad64_x3_kernel(WgradArgs a) {
             u32x4 hi, lo;
             split8(f, hi, lo);
             if (ty0 + row / TW >= a.H || tx0 + row % TW >= a.W) { hi = u32x4{0u, 0u, 0u, 0u}; lo = hi; }
-            *(u32x4*)(imgY + row * W64_PITCH + v * 16) = hi;
-            *(u32x4*)(imgY + PLY + row * W64_PITCH + v * 16) = lo;
+            x3_store<W64_PITCH>(imgY, PLY, row, v, hi, lo);
         }
 #pragma unroll
         for (int q = 0; q < NVX; ++q) {
@@ -498,8 +560,7 @@ __global__ __launch_bounds__(256) void wgrad64_x3_kernel(WgradArgs a) {
             split8(f, hi, lo);
             if (y < 0 || y >= a.H || x < 0 || x >= a.W) { hi = u32x4{0u, 0u, 0u, 0u}; lo = hi; }
             if (i < AROWS * 8) {
-                *(u32x4*)(imgA + row * W64_PITCH + v * 16) = hi;
-                *(u32x4*)(imgA + PLA + row * W64_PITCH + v * 16) = lo;
+                x3_store<W64_PITCH>(imgA, PLA, row, v, hi, lo);
             }
         }
         }
@@ -509,7 +570,8 @@ __global__ __launch_bounds__(256) void wgrad64_x3_kernel(WgradArgs a) {
             for (int p = 0; p < YROWS; ++p)
                 bias_acc += (float)*(const _Float16*)(imgY + p * W64_PITCH + tid * 2) + (float)*(const _Float16*)(imgY + PLY + p * W64_PITCH + tid * 2);
         }
-        // ---- MFMAs: small terms first, all three into the same accumulator ----
+        // ---- MFMAs: small terms first, all three into the same accumulator (mfma3 written out: with the helper the compiler schedules
+        // the nine-tap loop differently, and in wgrad64_x3_pc_kernel the one-tap loop; wgrad128_x3_pc_kernel calls it) ----
         const char* baseY = imgY + lane_off + coh * 64;
         const char* baseA = imgA + lane_off + cih * 64;
         if constexpr ((WGRAD_DBG & 1) == 0) {
@@ -517,7 +579,7 @@ __global__ __launch_bounds__(256) void wgrad64_x3_kernel(WgradArgs a) {
         for (int y = 0; y < WX_TH; ++y) {
 #pragma unroll
             for (int xb = 0; xb < TW; xb += 16) {
-                const tb_f16x8 fyh = frag(baseY + (y * TW + xb) * W64_PITCH), fyl = frag(baseY + PLY + (y * TW + xb) * W64_PITCH);
+                const x3_f16x8 fyh = tr_frag<x3_f16x8, W64_PITCH>(baseY + (y * TW + xb) * W64_PITCH), fyl = tr_frag<x3_f16x8, W64_PITCH>(baseY + PLY + (y * TW + xb) * W64_PITCH);
                 if constexpr (TAPS == 9) {
 #pragma unroll
                     for (int ky = 0; ky < 3; ++ky) {
@@ -525,7 +587,7 @@ __global__ __launch_bounds__(256) void wgrad64_x3_kernel(WgradArgs a) {
                         const TrWin wh = tr_load3(pa), wl = tr_load3(pa + PLA);
 #pragma unroll
                         for (int kx = 0; kx < 3; ++kx) {
-                            const tb_f16x8 fxh = tr_window<tb_f16x8>(wh, kx), fxl = tr_window<tb_f16x8>(wl, kx);
+                            const x3_f16x8 fxh = tr_window<x3_f16x8>(wh, kx), fxl = tr_window<x3_f16x8>(wl, kx);
                             f32x16& ac = acc[ky * 3 + kx];
                             ac = __builtin_amdgcn_mfma_f32_32x32x16_f16(fyl, fxh, ac, 0, 0, 0);
                             ac = __builtin_amdgcn_mfma_f32_32x32x16_f16(fyh, fxl, ac, 0, 0, 0);
@@ -534,7 +596,7 @@ __global__ __launch_bounds__(256) void wgrad64_x3_kernel(WgradArgs a) {
                     }
                 } else {
                     const char* pa = baseA + (y * AW + xb) * W64_PITCH;
-                    const tb_f16x8 fxh = frag(pa), fxl = frag(pa + PLA);
+                    const x3_f16x8 fxh = tr_frag<x3_f16x8, W64_PITCH>(pa), fxl = tr_frag<x3_f16x8, W64_PITCH>(pa + PLA);
                     acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fyl, fxh, acc[0], 0, 0, 0);
                     acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fyh, fxl, acc[0], 0, 0, 0);
                     acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fyh, fxh, acc[0], 0, 0, 0);
@@ -545,15 +607,14 @@ __global__ __launch_bounds__(256) void wgrad64_x3_kernel(WgradArgs a) {
     }
     // ---- this share's partial: [tap][64 co][64 ci] ----
     const int col = lane & 31;
-    float* out = a.part + ((size_t)share * npairs + pair) * TAPS * 4096;
+    float* out = a.part + ((size_t)share * npairs + pair) * TAPS * W64_N;
 #pragma unroll
     for (int t = 0; t < TAPS; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-            out[(size_t)t * 4096 + (coh * 32 + mfma32_row(r, h)) * 64 + cih * 32 + col] = acc[t][r] * yinv;
+            out[(size_t)t * W64_N + (coh * 32 + mfma32_row(r, h)) * 64 + cih * 32 + col] = acc[t][r] * yinv;
     if (a.part_bias && pair % nbc == 0 && tid < 64) a.part_bias[(size_t)share * a.Cout + co0 + tid] = bias_acc * yinv;
 }
-
 
 // ------------------------------------------------------------------------------------------------
 // fp16 x 3 weight gradient with SPECIALISED WAVES (round 5, second version; wgrad64_x3_kernel above is the first).
@@ -566,35 +627,18 @@ __global__ __launch_bounds__(256) void wgrad64_x3_kernel(WgradArgs a) {
 // Same arithmetic as wgrad64_x3_kernel per tile; the tile is half as high, so a share's partial is a sum over twice as many tiles in the
 // same order of pixels -- the rounding of the fp32 accumulation is that of a different tile split, results equal to fp32 round-off.
 // ------------------------------------------------------------------------------------------------
-constexpr int WP_TH = 2;
-
-// LDS traffic of this wave done, then the workgroup barrier; vector-memory loads stay in flight across it (__syncthreads() would
-// wait for the producers' prefetched global loads at every tile)
-__device__ __forceinline__ void wp_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
 template <int TAPS>
 __global__ __launch_bounds__(512) void wgrad64_x3_pc_kernel(WgradArgs a) {
     f16_saturate_mode();
-    constexpr int PAD = TAPS == 9 ? 1 : 0;
-    constexpr int AW = TW + 2 * PAD, AH = WP_TH + 2 * PAD, AROWS = AH * AW, YROWS = WP_TH * TW;
-    constexpr int NVX = (AROWS * 8 + 255) / 256, NVY = YROWS * 8 / 256;
-    constexpr int PLA = AROWS * W64_PITCH, PLY = YROWS * W64_PITCH;
-    constexpr int BUF = 2 * PLA + 2 * PLY;                   // one buffer: A hi, A lo, Y hi, Y lo
+    using L = W64PcLds<TAPS>;
+    constexpr int PAD = L::PAD, AW = L::AW, AROWS = L::AROWS, NVX = L::NVX, NVY = L::NVY, PLA = L::PLA, PLY = L::PLY;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool producer = wid >= 4;
     const int nbo = a.Cout / 64, nbc = a.Cin / 64, npairs = nbo * nbc;
     int share, pair;
-    {
-        const int L = blockIdx.x;
-        if (a.S % 8 == 0) { const int xcd = L & 7, j = L >> 3; share = (j / npairs) * 8 + xcd; pair = j % npairs; }
-        else { share = L / npairs; pair = L % npairs; }
-    }
+    wgrad_share_pair(a.S, npairs, share, pair);
     const int co0 = (pair / nbc) * 64, ci0 = (pair % nbc) * 64;
     const int tiles_x = (a.W + TW - 1) / TW, tiles_y = (a.H + WP_TH - 1) / WP_TH;
     const int tiles = a.B * tiles_x * tiles_y;
@@ -616,8 +660,8 @@ __global__ __launch_bounds__(512) void wgrad64_x3_pc_kernel(WgradArgs a) {
         int cur_b = -1;
         u32x4 vy[NVY][2], vx[NVX][2];
         auto issue_loads = [&](int tile) {
-            const int b = tile / (tiles_x * tiles_y), tt = tile % (tiles_x * tiles_y);
-            const int ty0 = (tt / tiles_x) * WP_TH, tx0 = (tt % tiles_x) * TW;
+            int b, ty0, tx0;
+            tile_origin<WP_TH>(tile, tiles_x, tiles_y, b, ty0, tx0);
 #pragma unroll
             for (int q = 0; q < NVY; ++q) {
                 const int row = (ptid + 256 * q) >> 3;
@@ -633,20 +677,13 @@ __global__ __launch_bounds__(512) void wgrad64_x3_pc_kernel(WgradArgs a) {
                 vx[q][0] = p[0]; vx[q][1] = p[1];
             }
         };
-        auto split8 = [](const float (&f)[8], u32x4& hi, u32x4& lo) {
-            tb_f16x8 hh, ll;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { hh[j] = (_Float16)f[j]; ll[j] = (_Float16)(f[j] - (float)hh[j]); }
-            hi = __builtin_bit_cast(u32x4, hh);
-            lo = __builtin_bit_cast(u32x4, ll);
-        };
         if (ntile > 0 && !(WGRAD_DBG & 4)) issue_loads(share);
         for (int it = 0; it < ntile; ++it) {
             const int tile = share + it * a.S;
-            const int b = tile / (tiles_x * tiles_y), tt = tile % (tiles_x * tiles_y);
-            const int ty0 = (tt / tiles_x) * WP_TH, tx0 = (tt % tiles_x) * TW;
-            char* imgA = smem + (it & 1) * BUF;
-            char* imgY = imgA + 2 * PLA;
+            int b, ty0, tx0;
+            tile_origin<WP_TH>(tile, tiles_x, tiles_y, b, ty0, tx0);
+            char* imgA = smem + (it & 1) * L::BUF + L::A;
+            char* imgY = smem + (it & 1) * L::BUF + L::Y;
             if (use_gn && b != cur_b) {                        // the affine of this thread's 8 channels (a few times per workgroup)
 #pragma unroll
                 for (int j = 0; j < 8; ++j) gn_scale_shift(a.st, a.B, b, a.Cin, ci0 + v * 8 + j, a.H * a.W, a.gamma, a.beta, sc[j], sh[j]);
@@ -667,8 +704,7 @@ __global__ __launch_bounds__(512) void wgrad64_x3_pc_kernel(WgradArgs a) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j) bias8[j] += f[j];
                 }
-                *(u32x4*)(imgY + row * W64_PITCH + v * 16) = hi;
-                *(u32x4*)(imgY + PLY + row * W64_PITCH + v * 16) = lo;
+                x3_store<W64_PITCH>(imgY, PLY, row, v, hi, lo);
             }
 #pragma unroll
             for (int q = 0; q < NVX; ++q) {
@@ -685,8 +721,7 @@ __global__ __launch_bounds__(512) void wgrad64_x3_pc_kernel(WgradArgs a) {
                 split8(f, hi, lo);
                 if (y < 0 || y >= a.H || x < 0 || x >= a.W) { hi = u32x4{0u, 0u, 0u, 0u}; lo = hi; }
                 if (i < AROWS * 8) {
-                    *(u32x4*)(imgA + row * W64_PITCH + v * 16) = hi;
-                    *(u32x4*)(imgA + PLA + row * W64_PITCH + v * 16) = lo;
+                    x3_store<W64_PITCH>(imgA, PLA, row, v, hi, lo);
                 }
             }
             }
@@ -708,24 +743,17 @@ __global__ __launch_bounds__(512) void wgrad64_x3_pc_kernel(WgradArgs a) {
             for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
         const int h = lane >> 5, g = (lane >> 4) & 1, i16 = lane & 15;
         const int lane_off = (8 * h + (i16 >> 2)) * W64_PITCH + (g * 16 + (i16 & 3) * 4) * 2;
-        auto frag = [&](const char* p) -> tb_f16x8 {
-            const tb_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p);
-            const tb_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 4 * W64_PITCH));
-            typedef short s16x8 __attribute__((ext_vector_type(8)));
-            const s16x8 vv = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-            return __builtin_bit_cast(tb_f16x8, vv);
-        };
         for (int it = 0; it < ntile; ++it) {
             wp_barrier();                                   // barrier `it`: buffer it % 2 is complete
-            const char* imgA = smem + (it & 1) * BUF;
-            const char* baseY = imgA + 2 * PLA + lane_off + coh * 64;
-            const char* baseA = imgA + lane_off + cih * 64;
+            const char* buf = smem + (it & 1) * L::BUF;
+            const char* baseY = buf + L::Y + lane_off + coh * 64;
+            const char* baseA = buf + L::A + lane_off + cih * 64;
             if constexpr ((WGRAD_DBG & 1) != 0) continue;
 #pragma unroll
             for (int y = 0; y < WP_TH; ++y) {
 #pragma unroll
                 for (int xb = 0; xb < TW; xb += 16) {
-                    const tb_f16x8 fyh = frag(baseY + (y * TW + xb) * W64_PITCH), fyl = frag(baseY + PLY + (y * TW + xb) * W64_PITCH);
+                    const x3_f16x8 fyh = tr_frag<x3_f16x8, W64_PITCH>(baseY + (y * TW + xb) * W64_PITCH), fyl = tr_frag<x3_f16x8, W64_PITCH>(baseY + PLY + (y * TW + xb) * W64_PITCH);
                     // (one fragment read pair per tap: sharing the reads between the three taps of a kernel row -- tr_load3 / tr_window, what
                     // wgrad64_x3_kernel does -- measured SLOWER here, 131 -> 137 us on the largest layer: the consumers are not bound by the
                     // number of LDS reads, and the funnel shifts sit in front of their MFMAs)
@@ -733,7 +761,7 @@ __global__ __launch_bounds__(512) void wgrad64_x3_pc_kernel(WgradArgs a) {
                     for (int t = 0; t < TAPS; ++t) {
                         const int ky = TAPS == 9 ? t / 3 : 0, kx = TAPS == 9 ? t % 3 : 0;
                         const char* pa = baseA + ((y + ky) * AW + xb + kx) * W64_PITCH;
-                        const tb_f16x8 fxh = frag(pa), fxl = frag(pa + PLA);
+                        const x3_f16x8 fxh = tr_frag<x3_f16x8, W64_PITCH>(pa), fxl = tr_frag<x3_f16x8, W64_PITCH>(pa + PLA);
                         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fyl, fxh, acc[t], 0, 0, 0);
                         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fyh, fxl, acc[t], 0, 0, 0);
                         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fyh, fxh, acc[t], 0, 0, 0);
@@ -743,21 +771,16 @@ __global__ __launch_bounds__(512) void wgrad64_x3_pc_kernel(WgradArgs a) {
         }
         wp_barrier();                                       // (pairs with the producers' final barrier)
         const int col = lane & 31;
-        float* out = a.part + ((size_t)share * npairs + pair) * TAPS * 4096;
+        float* out = a.part + ((size_t)share * npairs + pair) * TAPS * W64_N;
 #pragma unroll
         for (int t = 0; t < TAPS; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                out[(size_t)t * 4096 + (coh * 32 + mfma32_row(r, h)) * 64 + cih * 32 + col] = acc[t][r] * yinv;
+                out[(size_t)t * W64_N + (coh * 32 + mfma32_row(r, h)) * 64 + cih * 32 + col] = acc[t][r] * yinv;
     }
-    if (a.part_bias) {          // uniform.  dbias partial of this share: the producers' per-thread sums, added in thread order
+    if (a.part_bias) {          // uniform
         wp_barrier();
-        if (pair % nbc == 0 && tid < 64) {
-            float sum = 0.f;
-            const int vv = tid >> 3, j = tid & 7;              // channel tid = slot vv, element j
-            for (int p = 0; p < 32; ++p) sum += red[(p * 8 + vv) * 8 + j];
-            a.part_bias[(size_t)share * a.Cout + co0 + tid] = sum * yinv;
-        }
+        if (pair % nbc == 0 && tid < 64) pc_dbias<8>(a, red, share, co0, yinv, tid);
     }
 }
 
@@ -772,25 +795,19 @@ __global__ __launch_bounds__(512) void wgrad64_x3_pc_kernel(WgradArgs a) {
 // image); LDS rows are 320 bytes (256 + 64: the four rows a transposing read touches tile the 64 banks), two buffers of four planes
 // = 80 KB.  Roles, hand-over and arithmetic per product as in wgrad64_x3_pc_kernel; the partial sums are [share][pair][128][128].
 // ------------------------------------------------------------------------------------------------
-constexpr int W128_PITCH = 320, W128_PX = 32;
-
 __global__ __launch_bounds__(512) void wgrad128_x3_pc_kernel(WgradArgs a) {
     f16_saturate_mode();
+    using L = W128Lds;
     constexpr int CT = 128, SLOTS = CT / 8;                     // 8-channel slots per pixel row
     constexpr int NV = W128_PX * SLOTS / 256;                   // (pixel, 8 channels) units per producer thread, tile and operand
-    constexpr int PL = W128_PX * W128_PITCH;                    // one plane of a buffer
-    constexpr int BUF = 4 * PL;                                 // A hi, A lo, Y hi, Y lo
+    constexpr int PL = L::PL;                                   // one plane of a buffer
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool producer = wid >= 4;
     const int nbo = a.Cout / CT, nbc = a.Cin / CT, npairs = nbo * nbc;
     int share, pair;
-    {
-        const int L = blockIdx.x;
-        if (a.S % 8 == 0) { const int xcd = L & 7, j = L >> 3; share = (j / npairs) * 8 + xcd; pair = j % npairs; }
-        else { share = L / npairs; pair = L % npairs; }
-    }
+    wgrad_share_pair(a.S, npairs, share, pair);
     const int co0 = (pair / nbc) * CT, ci0 = (pair % nbc) * CT;
     const int HW = a.H * a.W;
     const int tiles = (int)(a.npix / W128_PX);
@@ -820,19 +837,12 @@ __global__ __launch_bounds__(512) void wgrad128_x3_pc_kernel(WgradArgs a) {
                 vx[q][0] = px[0]; vx[q][1] = px[1];
             }
         };
-        auto split8 = [](const float (&f)[8], u32x4& hi, u32x4& lo) {
-            tb_f16x8 hh, ll;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { hh[j] = (_Float16)f[j]; ll[j] = (_Float16)(f[j] - (float)hh[j]); }
-            hi = __builtin_bit_cast(u32x4, hh);
-            lo = __builtin_bit_cast(u32x4, ll);
-        };
         if (ntile > 0 && !(WGRAD_DBG & 4)) issue_loads(share);
         for (int it = 0; it < ntile; ++it) {
             const int tile = share + it * a.S;
             const int b = (int)(((size_t)tile * W128_PX) / HW);
-            char* imgA = smem + (it & 1) * BUF;
-            char* imgY = imgA + 2 * PL;
+            char* imgA = smem + (it & 1) * L::BUF + L::A;
+            char* imgY = smem + (it & 1) * L::BUF + L::Y;
             if (use_gn && b != cur_b) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) gn_scale_shift(a.st, a.B, b, a.Cin, ci0 + v * 8 + j, HW, a.gamma, a.beta, sc[j], sh[j]);
@@ -851,8 +861,7 @@ __global__ __launch_bounds__(512) void wgrad128_x3_pc_kernel(WgradArgs a) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j) bias8[j] += f[j];
                 }
-                *(u32x4*)(imgY + row * W128_PITCH + v * 16) = hi;
-                *(u32x4*)(imgY + PL + row * W128_PITCH + v * 16) = lo;
+                x3_store<W128_PITCH>(imgY, PL, row, v, hi, lo);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) { f[j] = __uint_as_float(vx[q][0][j]); f[4 + j] = __uint_as_float(vx[q][1][j]); }
                 if (use_gn) {
@@ -860,8 +869,7 @@ __global__ __launch_bounds__(512) void wgrad128_x3_pc_kernel(WgradArgs a) {
                     for (int j = 0; j < 8; ++j) { const float t = fmaf(f[j], sc[j], sh[j]); f[j] = t > 0.f ? t : 0.f; }
                 }
                 split8(f, hi, lo);
-                *(u32x4*)(imgA + row * W128_PITCH + v * 16) = hi;
-                *(u32x4*)(imgA + PL + row * W128_PITCH + v * 16) = lo;
+                x3_store<W128_PITCH>(imgA, PL, row, v, hi, lo);
             }
             }
             if constexpr ((WGRAD_DBG & 4) == 0) issue_loads(it + 1 < ntile ? tile + a.S : tile);      // in flight across the barrier and the next split
@@ -883,37 +891,26 @@ __global__ __launch_bounds__(512) void wgrad128_x3_pc_kernel(WgradArgs a) {
                 for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.f;
         const int h = lane >> 5, g = (lane >> 4) & 1, i16 = lane & 15;
         const int lane_off = (8 * h + (i16 >> 2)) * W128_PITCH + (g * 16 + (i16 & 3) * 4) * 2;
-        auto frag = [&](const char* p) -> tb_f16x8 {
-            const tb_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p);
-            const tb_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(p + 4 * W128_PITCH));
-            typedef short s16x8 __attribute__((ext_vector_type(8)));
-            const s16x8 vv = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-            return __builtin_bit_cast(tb_f16x8, vv);
-        };
         for (int it = 0; it < ntile; ++it) {
             wp_barrier();                                       // barrier `it`: buffer it % 2 is complete
-            const char* imgA = smem + (it & 1) * BUF;
-            const char* baseY = imgA + 2 * PL + lane_off + coh * 128;
-            const char* baseA = imgA + lane_off + cih * 128;
+            const char* buf = smem + (it & 1) * L::BUF;
+            const char* baseY = buf + L::Y + lane_off + coh * 128;
+            const char* baseA = buf + L::A + lane_off + cih * 128;
             if constexpr ((WGRAD_DBG & 1) != 0) continue;
 #pragma unroll
             for (int xb = 0; xb < W128_PX; xb += 16) {
-                tb_f16x8 fyh[2], fyl[2], fxh[2], fxl[2];
+                x3_f16x8 fyh[2], fyl[2], fxh[2], fxl[2];
 #pragma unroll
                 for (int m = 0; m < 2; ++m) {
-                    fyh[m] = frag(baseY + xb * W128_PITCH + m * 64);
-                    fyl[m] = frag(baseY + PL + xb * W128_PITCH + m * 64);
-                    fxh[m] = frag(baseA + xb * W128_PITCH + m * 64);
-                    fxl[m] = frag(baseA + PL + xb * W128_PITCH + m * 64);
+                    fyh[m] = tr_frag<x3_f16x8, W128_PITCH>(baseY + xb * W128_PITCH + m * 64);
+                    fyl[m] = tr_frag<x3_f16x8, W128_PITCH>(baseY + PL + xb * W128_PITCH + m * 64);
+                    fxh[m] = tr_frag<x3_f16x8, W128_PITCH>(baseA + xb * W128_PITCH + m * 64);
+                    fxl[m] = tr_frag<x3_f16x8, W128_PITCH>(baseA + PL + xb * W128_PITCH + m * 64);
                 }
 #pragma unroll
                 for (int m = 0; m < 2; ++m)
 #pragma unroll
-                    for (int n = 0; n < 2; ++n) {           // small terms first, all three into the same accumulator
-                        acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fyl[m], fxh[n], acc[m][n], 0, 0, 0);
-                        acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fyh[m], fxl[n], acc[m][n], 0, 0, 0);
-                        acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fyh[m], fxh[n], acc[m][n], 0, 0, 0);
-                    }
+                    for (int n = 0; n < 2; ++n) acc[m][n] = mfma3(fyh[m], fyl[m], fxh[n], fxl[n], acc[m][n]);
             }
         }
         wp_barrier();                                           // (pairs with the producers' final barrier)
@@ -927,55 +924,94 @@ __global__ __launch_bounds__(512) void wgrad128_x3_pc_kernel(WgradArgs a) {
                 for (int r = 0; r < 16; ++r)
                     out[(coh * 64 + m * 32 + mfma32_row(r, h)) * CT + cih * 64 + n * 32 + col] = acc[m][n][r] * yinv;
     }
-    if (a.part_bias) {          // uniform.  dbias partial of this share: the producers' per-thread sums, added in thread order
+    if (a.part_bias) {          // uniform
         wp_barrier();
-        if (pair % nbc == 0 && tid < CT) {
-            float sum = 0.f;
-            const int vv = tid >> 3, j = tid & 7;               // channel tid = slot vv, element j
-            for (int p = 0; p < 256 / SLOTS; ++p) sum += red[(p * SLOTS + vv) * 8 + j];
-            a.part_bias[(size_t)share * a.Cout + co0 + tid] = sum * yinv;
-        }
+        if (pair % nbc == 0 && tid < CT) pc_dbias<SLOTS>(a, red, share, co0, yinv, tid);
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// the launch plan (host): which kernel a layer runs and everything its launch and its workspace follow from
+// ------------------------------------------------------------------------------------------------
+struct WgradPlan {
+    int kernel, elem;                       // WGRAD_K_*; the arithmetic, CHORE_F32 / CHORE_BF16 / CHORE_F16X3
+    int taps, ct;                           // channel tile: ct x ct per workgroup
+    int th;                                 // rows of the pixel tile; 0: wgrad128_x3_pc_kernel's run of W128_PX pixels
+    int tiles, S;                           // pixel tiles, shares of them
+    size_t share_floats, part_floats;       // one share's partials [Cout/ct][Cin/ct][taps][ct][ct]; all S of them: where part_bias starts
+    size_t ws_bytes;                        // partials and [S][Cout] bias partials
+    dim3 grid, block;
+    size_t lds;                             // dynamic LDS bytes: the kernel's layout struct
+};
+
+static bool wgrad_use64(int dtype, int taps, int Cin, int Cout) {
+    return (dtype == CHORE_BF16 || dtype == CHORE_F16X3) && (taps == 9 || taps == 1) && Cin % 64 == 0 && Cout % 64 == 0;
+}
 static bool wgrad128_ok(int taps, int B, int H, int W, int Cin, int Cout) {
     static const bool off = getenv("CHORE_WGRAD_NO128") != nullptr;
     return !off && taps == 1 && Cin % 128 == 0 && Cout % 128 == 0 && ((long)H * W) % W128_PX == 0 && (long)B * H * W >= 8 * W128_PX;
 }
-static int wgrad128_shares(int B, int H, int W, int Cin, int Cout) {
-    const int tiles = (int)((long)B * H * W / W128_PX);
-    const int pairs = (Cout / 128) * (Cin / 128);
-    int S = ((256 + pairs - 1) / pairs + 7) / 8 * 8;
-    if (S > tiles) S = tiles;
-    return S;
-}
-
-static int wgrad64_x3_pc_shares(int B, int H, int W, int Cin, int Cout) {
-    const int tiles = B * ((W + TW - 1) / TW) * ((H + WP_TH - 1) / WP_TH);
-    const int pairs = (Cout / 64) * (Cin / 64);
-    int S = ((256 + pairs - 1) / pairs + 7) / 8 * 8;
-    if (S > tiles) S = tiles;
-    return S;
-}
-
-static int wgrad64_x3_shares(int B, int H, int W, int Cin, int Cout) {
-    const int tiles = B * ((W + TW - 1) / TW) * ((H + WX_TH - 1) / WX_TH);
-    const int pairs = (Cout / 64) * (Cin / 64);
-    int S = ((256 + pairs - 1) / pairs + 7) / 8 * 8;
-    if (S > tiles) S = tiles;
-    return S;
-}
-
-static int wgrad64_shares(int B, int H, int W, int Cin, int Cout) {
+// shares of the pixel tiles, wgrad_kernel: enough workgroups to fill the chip, at least 4 tiles per share
+static int wgrad_shares(int B, int H, int W, int Cin, int Cout) {
     const int tiles = B * ((W + TW - 1) / TW) * ((H + TH - 1) / TH);
-    const int pairs = (Cout / 64) * (Cin / 64);
+    const int pairs = (Cout / 32) * (Cin / 32);
+    int S = (1024 + pairs - 1) / pairs;
+    if (S > tiles / 2) S = tiles / 2;
+    if (S < 1) S = 1;
+    return S;
+}
+// ... the 64- and 128-channel kernels: 256 workgroups or more, a multiple of 8 (wgrad_xcd_mapping), at most one share per tile
+static int wgrad_shares_xcd(int tiles, int pairs) {
     int S = ((256 + pairs - 1) / pairs + 7) / 8 * 8;
     if (S > tiles) S = tiles;
     return S;
 }
-static bool wgrad_use64(int dtype, int taps, int Cin, int Cout) {
-    return (dtype == CHORE_BF16 || dtype == CHORE_F16X3) && (taps == 9 || taps == 1) && Cin % 64 == 0 && Cout % 64 == 0;
+static size_t wgrad_lds_bytes(int kernel, int elem, int taps) {
+    const bool t9 = taps == 9;
+    switch (kernel) {
+    case WGRAD_K_W64: return t9 ? W64Lds<9>::BYTES : W64Lds<1>::BYTES;
+    case WGRAD_K_W64X3: return t9 ? W64X3Lds<9>::BYTES : W64X3Lds<1>::BYTES;
+    case WGRAD_K_W64X3PC: return t9 ? W64PcLds<9>::BYTES : W64PcLds<1>::BYTES;
+    case WGRAD_K_W128X3PC: return W128Lds::BYTES;
+    }
+    if (elem == CHORE_F32) return t9 ? W32Lds<float, 9>::BYTES : W32Lds<float, 1>::BYTES;
+    return t9 ? W32Lds<bf16_t, 9>::BYTES : W32Lds<bf16_t, 1>::BYTES;
 }
+// `kernel` on a layer it accepts (64 | Cin, Cout for the 64-channel kernels, wgrad128_ok for the 128-channel one)
+static WgradPlan wgrad_describe(int kernel, int elem, int taps, int B, int H, int W, int Cin, int Cout) {
+    WgradPlan p;
+    p.kernel = kernel; p.elem = elem; p.taps = taps;
+    p.ct = kernel == WGRAD_K_W32 ? CT32 : kernel == WGRAD_K_W128X3PC ? 128 : 64;
+    p.th = kernel == WGRAD_K_W64X3 ? WX_TH : kernel == WGRAD_K_W64X3PC ? WP_TH : kernel == WGRAD_K_W128X3PC ? 0 : TH;
+    p.tiles = p.th ? B * ((W + TW - 1) / TW) * ((H + p.th - 1) / p.th) : (int)((long)B * H * W / W128_PX);
+    const int pairs = (Cout / p.ct) * (Cin / p.ct);
+    p.S = kernel == WGRAD_K_W32 ? wgrad_shares(B, H, W, Cin, Cout) : wgrad_shares_xcd(p.tiles, pairs);
+    p.share_floats = (size_t)pairs * taps * p.ct * p.ct;
+    p.part_floats = (size_t)p.S * p.share_floats;
+    p.ws_bytes = (p.part_floats + (size_t)p.S * Cout) * sizeof(float);
+    p.grid = kernel == WGRAD_K_W32 ? dim3(Cout / CT32, Cin / CT32, p.S) : dim3(p.S * pairs);
+    p.block = dim3(kernel == WGRAD_K_W64X3PC || kernel == WGRAD_K_W128X3PC ? 512 : 256);
+    p.lds = wgrad_lds_bytes(kernel, elem, taps);
+    return p;
+}
+// the dispatch: the one place that picks a layer's kernel
+static WgradPlan wgrad_plan(int dtype, int taps, int B, int H, int W, int Cin, int Cout) {
+    // channel counts below 64 (the 256^2 block) run wgrad_kernel; in the fp16 x 3 mode that is the exact fp32 matrix-core kernel
+    int kernel = WGRAD_K_W32, elem = dtype == CHORE_F16X3 ? CHORE_F32 : dtype;
+    if (wgrad_use64(dtype, taps, Cin, Cout)) {
+        elem = dtype;
+        // which fp16 x 3 kernel: the specialised-wave one where it measured faster alone (profiles/r05_wgrad_x3.txt: the 1x1 layers
+        // 101 -> 85 us, 3x3 256->128 at 128^2 150 -> 131, 128->128 90 -> 82; the 64-channel layers and the 32^2 maps are 2 - 8 us
+        // SLOWER on it: twice the tiles, twice the barriers).  CHORE_WGRAD_X3_V1=1 / CHORE_WGRAD_X3_PC=1 force one of them.
+        static const bool x3_v1 = getenv("CHORE_WGRAD_X3_V1") != nullptr, x3_pc = getenv("CHORE_WGRAD_X3_PC") != nullptr;
+        const bool use_pc = x3_pc || (!x3_v1 && (taps == 1 || (Cin >= 128 && Cout >= 128 && (long)H * W >= 128 * 128)));
+        if (dtype == CHORE_BF16) kernel = WGRAD_K_W64;
+        else if (!x3_v1 && !x3_pc && wgrad128_ok(taps, B, H, W, Cin, Cout)) kernel = WGRAD_K_W128X3PC;      // the 1 x 1 layers: 128 x 128-channel tiles
+        else kernel = use_pc ? WGRAD_K_W64X3PC : WGRAD_K_W64X3;
+    }
+    return wgrad_describe(kernel, elem, taps, B, H, W, Cin, Cout);
+}
+constexpr int wgrad_inst(int kernel, int elem, int taps) { return (kernel * 4 + elem) * 16 + taps; }      // one template instantiation
 
 // dW (O,C,kh,kw) = sum over the shares, in order
 __device__ __forceinline__ void wgrad_finish_body(size_t i, const float* __restrict__ part, const float* __restrict__ part_bias,
@@ -1269,32 +1305,22 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const T* __restrict__
 
 extern "C" {
 
-// shares of the pixel tiles: enough workgroups to fill the chip, at least 4 tiles per share
-static int wgrad_shares(int B, int H, int W, int Cin, int Cout) {
-    const int tiles = B * ((W + TW - 1) / TW) * ((H + TH - 1) / TH);
-    const int pairs = (Cout / 32) * (Cin / 32);
-    int S = (1024 + pairs - 1) / pairs;
-    if (S > tiles / 2) S = tiles / 2;
-    if (S < 1) S = 1;
-    return S;
-}
-
+// the largest plan of the kernels the layer can reach in any mode and under any switch that forces one of them
 size_t chore_conv2d_wgrad_workspace_bytes(int taps, int B, int H, int W, int Cin, int Cout) {
     if ((taps != 1 && taps != 9) || Cin % 32 || Cout % 32 || B <= 0) return 0;
-    const int S = wgrad_shares(B, H, W, Cin, Cout);
-    size_t n = (size_t)S * (Cout / 32) * (Cin / 32) * taps * 1024 + (size_t)S * Cout;
-    if (wgrad_use64(CHORE_BF16, taps, Cin, Cout)) {       // the bf16 path of these shapes uses 64-channel tiles
-        const int Sb = wgrad64_shares(B, H, W, Cin, Cout), Sx = wgrad64_x3_shares(B, H, W, Cin, Cout), Sp = wgrad64_x3_pc_shares(B, H, W, Cin, Cout);
-        const int S64 = (Sb > Sx ? Sb : Sx) > Sp ? (Sb > Sx ? Sb : Sx) : Sp;
-        const size_t n64 = (size_t)S64 * (Cout / 64) * (Cin / 64) * taps * 4096 + (size_t)S64 * Cout;
-        if (n64 > n) n = n64;
+    size_t n = 0;
+    auto cover = [&](int kernel, int elem) {
+        const size_t m = wgrad_describe(kernel, elem, taps, B, H, W, Cin, Cout).ws_bytes;
+        if (m > n) n = m;
+    };
+    cover(WGRAD_K_W32, CHORE_F32);
+    if (wgrad_use64(CHORE_BF16, taps, Cin, Cout)) {       // the 16-bit paths of these shapes use 64-channel tiles
+        cover(WGRAD_K_W64, CHORE_BF16);
+        cover(WGRAD_K_W64X3, CHORE_F16X3);
+        cover(WGRAD_K_W64X3PC, CHORE_F16X3);
     }
-    if (wgrad128_ok(taps, B, H, W, Cin, Cout)) {
-        const int S128 = wgrad128_shares(B, H, W, Cin, Cout);
-        const size_t n128 = (size_t)S128 * (Cout / 128) * (Cin / 128) * 16384 + (size_t)S128 * Cout;
-        if (n128 > n) n = n128;
-    }
-    return n * sizeof(float);
+    if (wgrad128_ok(taps, B, H, W, Cin, Cout)) cover(WGRAD_K_W128X3PC, CHORE_F16X3);
+    return n;
 }
 
 }  // extern "C"
@@ -1345,84 +1371,41 @@ int conv2d_bwd_weight_impl(chore_handle* h, int dtype, int taps, const void* x, 
     if ((taps != 1 && taps != 9) || Cin % 32 || Cout % 32 || Cin > 256)
         CHORE_FAIL(h, CHORE_EINVAL, "chore_conv2d_bwd_weight: unsupported taps=%d Cin=%d Cout=%d", taps, Cin, Cout);
     if (dtype != CHORE_F32 && dtype != CHORE_BF16 && dtype != CHORE_F16X3) CHORE_FAIL(h, CHORE_EINVAL, "chore_conv2d_bwd_weight: bad dtype");
+    const WgradPlan p = wgrad_plan(dtype, taps, B, H, W, Cin, Cout);
     WgradArgs a;
     a.dy_amax = dy_amax;
     a.x = x; a.st = (const GroupStat*)stats; a.gamma = gamma; a.beta = beta; a.dy = dy;
     a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
     a.xs = Cin; a.ys = dy_stride; a.npix = (long long)B * H * W;
     a.part = (float*)workspace;
-    int ct = 32;
-    // the witness of this launch (chore_debug_last_wgrad; host stores only): th = rows of the kernel's pixel tile
-    const int wflags = (stats ? WGRAD_FLAG_GN : 0) | (dbias ? WGRAD_FLAG_DBIAS : 0);
-    auto note = [&](int kernel, int elem, int th) {
-        const int tiles = kernel == WGRAD_K_W128X3PC ? (int)((long)B * H * W / W128_PX) : B * ((W + TW - 1) / TW) * ((H + th - 1) / th);
-        chore_note_wgrad(h, kernel, elem, taps, ct, a.S, tiles, wflags | (ct >= 64 && a.S % 8 == 0 ? WGRAD_FLAG_XCD : 0));
-    };
-    // after a layer's partial sums are launched (rc: that launch's result): the sum over the shares now, or, with `defer`, a
-    // record of it for launch_wgrad_finish_multi
-    auto finish = [&](int rc) -> int {
-        if (rc) return rc;
-        if (defer) { defer->j[defer->n++] = {a.part, a.part_bias, dw, dbias, a.S, Cout, Cin, taps, ct}; return CHORE_OK; }
-        const size_t n = (size_t)Cout * Cin * taps;
-        hipLaunchKernelGGL(wgrad_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.part, a.part_bias, a.S, Cout,
-                           Cin, taps, dw, dbias, ct);
-        CHORE_LAUNCH_CHECK(h, s);
-        return CHORE_OK;
-    };
-    if (wgrad_use64(dtype, taps, Cin, Cout)) {
-        ct = 64;
-        const bool x3 = dtype == CHORE_F16X3;
-        a.S = x3 ? wgrad64_x3_shares(B, H, W, Cin, Cout) : wgrad64_shares(B, H, W, Cin, Cout);
-        const int npairs = (Cout / 64) * (Cin / 64);
-        a.part_bias = dbias ? a.part + (size_t)a.S * npairs * taps * 4096 : nullptr;
-        // which fp16 x 3 kernel: the specialised-wave one where it measured faster alone (profiles/r05_wgrad_x3.txt: the 1x1 layers
-        // 101 -> 85 us, 3x3 256->128 at 128^2 150 -> 131, 128->128 90 -> 82; the 64-channel layers and the 32^2 maps are 2 - 8 us
-        // SLOWER on it: twice the tiles, twice the barriers).  CHORE_WGRAD_X3_V1=1 / CHORE_WGRAD_X3_PC=1 force one of them.
-        static const bool x3_v1 = getenv("CHORE_WGRAD_X3_V1") != nullptr, x3_pc = getenv("CHORE_WGRAD_X3_PC") != nullptr;
-        const bool use_pc = x3_pc || (!x3_v1 && (taps == 1 || (Cin >= 128 && Cout >= 128 && (long)H * W >= 128 * 128)));
-        if (x3 && !x3_v1 && !x3_pc && wgrad128_ok(taps, B, H, W, Cin, Cout)) {      // the 1 x 1 layers: 128 x 128-channel tiles
-            ct = 128;
-            a.S = wgrad128_shares(B, H, W, Cin, Cout);
-            const int np128 = (Cout / 128) * (Cin / 128);
-            a.part_bias = dbias ? a.part + (size_t)a.S * np128 * 16384 : nullptr;
-            const size_t sm128 = (size_t)2 * 4 * W128_PX * W128_PITCH;
-            note(WGRAD_K_W128X3PC, CHORE_F16X3, 1);
-            return finish(CHORE_LAUNCH(h, s, wgrad128_x3_pc_kernel, dim3(a.S * np128), dim3(512), sm128, a));
-        }
-        if (x3 && use_pc) {
-            a.S = wgrad64_x3_pc_shares(B, H, W, Cin, Cout);
-            a.part_bias = dbias ? a.part + (size_t)a.S * npairs * taps * 4096 : nullptr;
-            const size_t arows = taps == 9 ? (size_t)(WP_TH + 2) * PW : (size_t)WP_TH * TW;
-            const size_t smp = (size_t)2 * 2 * (arows + WP_TH * TW) * W64_PITCH;
-            note(WGRAD_K_W64X3PC, CHORE_F16X3, WP_TH);
-            return finish(taps == 9 ? CHORE_LAUNCH(h, s, wgrad64_x3_pc_kernel<9>, dim3(a.S * npairs), dim3(512), smp, a)
-                                    : CHORE_LAUNCH(h, s, wgrad64_x3_pc_kernel<1>, dim3(a.S * npairs), dim3(512), smp, a));
-        }
-        if (x3) {
-            const size_t smx = (size_t)2 * ((taps == 9 ? (WX_TH + 2) * PW : WX_TH * TW) + WX_TH * TW) * W64_PITCH + 64 * 2 * sizeof(float);
-            note(WGRAD_K_W64X3, CHORE_F16X3, WX_TH);
-            return finish(taps == 9 ? CHORE_LAUNCH(h, s, wgrad64_x3_kernel<9>, dim3(a.S * npairs), dim3(256), smx, a)
-                                    : CHORE_LAUNCH(h, s, wgrad64_x3_kernel<1>, dim3(a.S * npairs), dim3(256), smx, a));
-        }
-        const size_t smem64 = (size_t)((taps == 9 ? PH * PW : TH * TW) + TH * TW) * W64_PITCH + 64 * 2 * sizeof(float);
-        note(WGRAD_K_W64, CHORE_BF16, TH);
-        return finish(taps == 9 ? CHORE_LAUNCH(h, s, wgrad64_kernel<9>, dim3(a.S * npairs), dim3(256), smem64, a)
-                                : CHORE_LAUNCH(h, s, wgrad64_kernel<1>, dim3(a.S * npairs), dim3(256), smem64, a));
+    a.part_bias = dbias ? a.part + p.part_floats : nullptr;
+    a.S = p.S;
+    // the witness of this launch (chore_debug_last_wgrad; host stores only)
+    chore_note_wgrad(h, p.kernel, p.elem, taps, p.ct, p.S, p.tiles,
+                     (stats ? WGRAD_FLAG_GN : 0) | (dbias ? WGRAD_FLAG_DBIAS : 0) | (p.ct >= 64 && wgrad_xcd_mapping(p.S) ? WGRAD_FLAG_XCD : 0));
+    int rc;
+    switch (wgrad_inst(p.kernel, p.elem, taps)) {
+    default: CHORE_FAIL(h, CHORE_EINVAL, "chore_conv2d_bwd_weight: no kernel for this plan");
+    case wgrad_inst(WGRAD_K_W32, CHORE_F32, 9): rc = CHORE_LAUNCH(h, s, (wgrad_kernel<float, 9>), p.grid, p.block, p.lds, a); break;
+    case wgrad_inst(WGRAD_K_W32, CHORE_F32, 1): rc = CHORE_LAUNCH(h, s, (wgrad_kernel<float, 1>), p.grid, p.block, p.lds, a); break;
+    case wgrad_inst(WGRAD_K_W32, CHORE_BF16, 9): rc = CHORE_LAUNCH(h, s, (wgrad_kernel<bf16_t, 9>), p.grid, p.block, p.lds, a); break;
+    case wgrad_inst(WGRAD_K_W32, CHORE_BF16, 1): rc = CHORE_LAUNCH(h, s, (wgrad_kernel<bf16_t, 1>), p.grid, p.block, p.lds, a); break;
+    case wgrad_inst(WGRAD_K_W64, CHORE_BF16, 9): rc = CHORE_LAUNCH(h, s, wgrad64_kernel<9>, p.grid, p.block, p.lds, a); break;
+    case wgrad_inst(WGRAD_K_W64, CHORE_BF16, 1): rc = CHORE_LAUNCH(h, s, wgrad64_kernel<1>, p.grid, p.block, p.lds, a); break;
+    case wgrad_inst(WGRAD_K_W64X3, CHORE_F16X3, 9): rc = CHORE_LAUNCH(h, s, wgrad64_x3_kernel<9>, p.grid, p.block, p.lds, a); break;
+    case wgrad_inst(WGRAD_K_W64X3, CHORE_F16X3, 1): rc = CHORE_LAUNCH(h, s, wgrad64_x3_kernel<1>, p.grid, p.block, p.lds, a); break;
+    case wgrad_inst(WGRAD_K_W64X3PC, CHORE_F16X3, 9): rc = CHORE_LAUNCH(h, s, wgrad64_x3_pc_kernel<9>, p.grid, p.block, p.lds, a); break;
+    case wgrad_inst(WGRAD_K_W64X3PC, CHORE_F16X3, 1): rc = CHORE_LAUNCH(h, s, wgrad64_x3_pc_kernel<1>, p.grid, p.block, p.lds, a); break;
+    case wgrad_inst(WGRAD_K_W128X3PC, CHORE_F16X3, 1): rc = CHORE_LAUNCH(h, s, wgrad128_x3_pc_kernel, p.grid, p.block, p.lds, a); break;
     }
-    if (dtype == CHORE_F16X3) dtype = CHORE_F32;      // channel counts below 64 (the 256^2 block): the exact fp32 matrix-core kernel
-    a.S = wgrad_shares(B, H, W, Cin, Cout);
-    a.part_bias = dbias ? a.part + (size_t)a.S * (Cout / 32) * (Cin / 32) * taps * 1024 : nullptr;
-    const size_t es = dtype == CHORE_F32 ? 4 : 2;
-    const int arows = taps == 9 ? PH * PW : TH * TW;
-    size_t smem = (size_t)(arows + TH * TW) * CT32 * es + 256;
-    if (smem < 4 * 1024 * sizeof(float)) smem = 4 * 1024 * sizeof(float);
-    dim3 grid(Cout / 32, Cin / 32, a.S);
-    note(WGRAD_K_W32, dtype, TH);
-    if (dtype == CHORE_F32)
-        return finish(taps == 9 ? CHORE_LAUNCH(h, s, (wgrad_kernel<float, 9>), grid, dim3(256), smem, a)
-                                : CHORE_LAUNCH(h, s, (wgrad_kernel<float, 1>), grid, dim3(256), smem, a));
-    return finish(taps == 9 ? CHORE_LAUNCH(h, s, (wgrad_kernel<bf16_t, 9>), grid, dim3(256), smem, a)
-                            : CHORE_LAUNCH(h, s, (wgrad_kernel<bf16_t, 1>), grid, dim3(256), smem, a));
+    if (rc) return rc;
+    // finish: the sum over the shares now, or, with `defer`, a record of it for launch_wgrad_finish_multi
+    if (defer) { defer->j[defer->n++] = {a.part, a.part_bias, dw, dbias, a.S, Cout, Cin, taps, p.ct}; return CHORE_OK; }
+    const size_t n = (size_t)Cout * Cin * taps;
+    hipLaunchKernelGGL(wgrad_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.part, a.part_bias, a.S, Cout,
+                       Cin, taps, dw, dbias, p.ct);
+    CHORE_LAUNCH_CHECK(h, s);
+    return CHORE_OK;
 }
 
 int launch_wgrad_finish_multi(chore_handle* h, const WgradFinishJobs& jobs, hipStream_t s) {
@@ -1455,8 +1438,7 @@ int chore_conv2d_bwd_weight(chore_handle* h, int dtype, int taps, const void* x,
 // GEMM took 14 ms per product there.
 size_t chore_gemm_tn_workspace_bytes(int P, int M, int N) {
     if (P <= 0 || M % 32 || N % 32) return 0;
-    const int S = wgrad_shares(1, (P + 31) / 32, 32, N, M);
-    return (size_t)S * (M / 32) * (N / 32) * 1024 * sizeof(float);
+    return wgrad_describe(WGRAD_K_W32, CHORE_F32, 1, 1, (P + 31) / 32, 32, N, M).part_floats * sizeof(float);      // (no bias partials)
 }
 
 int chore_gemm_tn_f32(chore_handle* h, const float* A, int lda, const float* B, int ldb, int P, int M, int N, float* C,
@@ -1470,12 +1452,12 @@ int chore_gemm_tn_f32(chore_handle* h, const float* A, int lda, const float* B, 
     a.dy_amax = nullptr;
     a.x = B; a.st = nullptr; a.gamma = nullptr; a.beta = nullptr; a.dy = A;
     a.B = 1; a.H = (P + 31) / 32; a.W = 32; a.Cin = N; a.Cout = M; a.xs = ldb; a.ys = lda; a.npix = P;
-    a.S = wgrad_shares(1, a.H, a.W, N, M);
+    const WgradPlan p = wgrad_describe(WGRAD_K_W32, CHORE_F32, 1, a.B, a.H, a.W, N, M);      // S = wgrad_shares(1, ceil(P / 32), 32, N, M)
+    a.S = p.S;
     a.part = (float*)workspace;
     a.part_bias = nullptr;
-    const size_t smem = (size_t)(2 * TH * TW) * CT32 * 4 + 256;
-    chore_note_wgrad(h, WGRAD_K_W32, CHORE_F32, 1, 32, a.S, (a.H + TH - 1) / TH, 0);
-    if (int rc = CHORE_LAUNCH(h, s, (wgrad_kernel<float, 1>), dim3(M / 32, N / 32, a.S), dim3(256), smem, a)) return rc;
+    chore_note_wgrad(h, p.kernel, p.elem, 1, p.ct, p.S, p.tiles, 0);
+    if (int rc = CHORE_LAUNCH(h, s, (wgrad_kernel<float, 1>), p.grid, p.block, p.lds, a)) return rc;
     const size_t n = (size_t)M * N;
     hipLaunchKernelGGL(wgrad_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.part, nullptr, a.S, M, N, 1, C,
                        nullptr, 32);

@@ -60,9 +60,22 @@ def test_table_names_every_launched_instantiation():
 
 def test_mapping_rule_and_witness_codes_are_the_sources():
     src = _src()
-    # the two block -> (share, pair) mappings of the 64- and 128-channel kernels, chosen by S % 8 as the witness flag says
-    assert src.count("if (a.S % 8 == 0) { const int xcd = L & 7") == 4
-    assert "ct >= 64 && a.S % 8 == 0 ? WGRAD_FLAG_XCD : 0" in src
+    # the two block -> (share, pair) mappings of the 64- and 128-channel kernels, chosen by S % 8 as the witness flag says: one
+    # predicate, one mapping helper that applies it, and the witness flag computed through the same predicate
+    assert len(re.findall(r"\bwgrad_xcd_mapping\(int S\)", src)) == 1
+    assert "__host__ __device__ inline bool wgrad_xcd_mapping(int S) { return S % 8 == 0; }" in src
+    assert src.count("S % 8 == 0") == 1
+    helper = _body(src, "__device__ __forceinline__ void wgrad_share_pair(")
+    assert src.count("const int xcd = L & 7") == 1 and "if (wgrad_xcd_mapping(S)) { const int xcd = L & 7" in helper
+    assert helper.count("blockIdx.x") == 1
+    for kern in NAMES:
+        body = _body(src, "void %s(WgradArgs a)" % kern)
+        if kern == "wgrad_kernel":
+            assert "wgrad_share_pair" not in body and "wgrad_xcd_mapping" not in body
+        else:
+            assert body.count("wgrad_share_pair(a.S, npairs, share, pair);") == body.count("wgrad_share_pair") == 1, kern
+            assert "blockIdx.x" not in body and "wgrad_xcd_mapping" not in body, kern
+    assert "p.ct >= 64 && wgrad_xcd_mapping(p.S) ? WGRAD_FLAG_XCD : 0" in _body(src, "int conv2d_bwd_weight_impl(")
     common = open(os.path.join(REPO, "chore_amd", "csrc", "common.h")).read()
     m = re.search(r"enum \{ WGRAD_K_W32 = (\d), WGRAD_K_W64 = (\d), WGRAD_K_W64X3 = (\d), WGRAD_K_W64X3PC = (\d), WGRAD_K_W128X3PC = (\d) \};", common)
     assert m and {int(v): k for v, k in zip(m.groups(), ("w32", "w64", "w64x3", "w64x3pc", "w128x3pc"))} == wc.KERNELS

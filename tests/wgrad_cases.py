@@ -5,7 +5,7 @@ channels `cout`, batch and map size, whether dbias is asked for, and a kind:
   "gn"     x random, GroupNorm + ReLU recomputed on it, dy random                 -> compared within the stated bounds
   "exact"  no GroupNorm, x and dy in {-1, 0, 1}                                   -> compared bit for bit
   "zero"   GroupNorm recomputed on a random x, dy == 0                            -> dW and dbias exactly 0
-The shapes were chosen by reading the dispatch of conv2d_bwd_weight_impl and the *_shares functions; which kernel each one
+The shapes were chosen by reading wgrad_plan (the dispatch) and wgrad_shares / wgrad_shares_xcd (the share counts); which kernel each one
 reaches is not asserted per case but through COVERAGE: every row marked to-reach must have been reported by
 chore_debug_last_wgrad for at least one case of the run.
 
