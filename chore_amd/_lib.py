@@ -212,6 +212,8 @@ SIGNATURES = {
                                [c_float] * 4 + [c_void_p] * 2 + [c_int] + [c_void_p] * 6),
     "chore_mesh_dist_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "chore_mesh_dist_fwd": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 6),
+    "chore_mesh_sdf_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "chore_mesh_sdf_fwd": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 7),
     "chore_contact_workspace_bytes":(c_size_t, [c_int, c_int, c_int, c_int]),
     "chore_contact_fwd": (c_int, [c_void_p] * 7 + [c_int] * 4 + [c_float, c_void_p, c_void_p, c_void_p]),
     "chore_contact_bwd": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 5),

@@ -19,6 +19,18 @@
 //                   minimum of keys is "smallest fp32 squared distance, then smallest face index".
 //   finish_kernel   minimum over the chunks' keys, sqrt, closest point of the winning triangle (same arithmetic).
 //   vertex_kernel   nearest vertex, tiled through LDS, first smallest squared distance (only when vert_idx is asked for).
+//
+// chore_mesh_sdf_fwd is the same call plus the generalized winding number (Jacobson et al. 2013): the WIND instantiations of the
+// three kernels' bodies (record_kernel_w, dist_kernel_w, finish_kernel_w).  In the loop of dist_kernel_w every triangle also adds
+// atan2(a.(b x c), |a||b||c| + (a.b)|c| + (a.c)|b| + (b.c)|a|), half its signed solid angle (van Oosterom & Strackee 1983; a, b,
+// c = corners minus the point), to a per-point float; every (chunk, point) stores that partial sum beside its key and
+// finish_kernel_w adds the chunks in ascending order and divides by 2 pi: no atomics, the bits depend on the shapes and the inputs alone.  a, b, c are formed from the corners themselves (a second
+// record per triangle, RecW, beside the first in LDS), one rounding each and the same value in every triangle that shares the
+// corner: next to an edge the two large angles of its triangles then err alike and cancel, which a + ab - p would not give.
+// A triangle whose fp32 edges ab, ac are exactly parallel (repeated index, zero area; recognised in fp64 by record_kernel,
+// RecW::area = 0) has its determinant forced to +-0, a point on a corner has one of a, b, c = 0: the determinant is +-0 and the
+// denominator +0, so atan2 gives +-0 without a special case.
+// The unsigned instantiations are the kernels as they were (same registers, LDS, occupancy: DESIGN.md, 'Mesh distance').
 #include "common.h"
 
 namespace {
@@ -38,7 +50,12 @@ struct Rec {
     float k1, k2, k3;               // v = k1 d1 - k2 d2, w = k3 d2 - k2 d1 with d1 = ab.ap, d2 = ac.ap; all 0 = no interior
     float pad;
 };
+struct RecW {                       // chore_mesh_sdf_fwd only: corners b and c (a is in Rec), 1 = has an area / 0 = ab x ac is exactly 0
+    float bx, by, bz, cx, cy, cz, area, pad;
+};
+constexpr int MD_RECW = 8;          // floats per RecW
 static_assert(sizeof(Rec) == MD_REC * sizeof(float), "one record is one 64-byte line");
+static_assert(sizeof(RecW) == MD_RECW * sizeof(float), "two RecW are one 64-byte line");
 
 // the number of face chunks: a function of the shapes alone (the workspace size and the result's bits depend on it)
 __host__ __device__ inline int md_chunks(int B, int N, int F) {
@@ -66,8 +83,11 @@ __device__ __forceinline__ float guarded_recip(double x) {
     return r < 3.0e38f ? r : 0.f;
 }
 
-__global__ __launch_bounds__(256) void record_kernel(const float* __restrict__ verts, const int* __restrict__ faces, int V, int F,
-                                                     Rec* __restrict__ rec) {
+// The bodies of the three kernels are templates; the __global__ functions below them are the two instantiations, the unsigned
+// ones under the names and with the parameters they always had.
+template <bool WIND>
+__device__ __forceinline__ void record_body(const float* __restrict__ verts, const int* __restrict__ faces, int V, int F,
+                                            Rec* __restrict__ rec, RecW* __restrict__ recw) {
     const int f = blockIdx.x * 256 + threadIdx.x;
     if (f >= F) return;
     const int b = blockIdx.y;
@@ -94,6 +114,23 @@ __global__ __launch_bounds__(256) void record_kernel(const float* __restrict__ v
     r.k1 = k1, r.k2 = k2, r.k3 = k3;
     r.pad = 0.f;
     rec[(size_t)b * F + f] = r;
+    if constexpr (WIND) {   // products of fp32 values are exact in fp64: every component is 0 only if ab and ac are exactly parallel
+        const double nx = aby * acz - abz * acy, ny = abz * acx - abx * acz, nz = abx * acy - aby * acx;
+        RecW w;
+        w.bx = vb[i1 * 3], w.by = vb[i1 * 3 + 1], w.bz = vb[i1 * 3 + 2];
+        w.cx = vb[i2 * 3], w.cy = vb[i2 * 3 + 1], w.cz = vb[i2 * 3 + 2];
+        w.area = (nx != 0.0 || ny != 0.0 || nz != 0.0) ? 1.f : 0.f;
+        w.pad = 0.f;
+        recw[(size_t)b * F + f] = w;
+    }
+}
+__global__ __launch_bounds__(256) void record_kernel(const float* __restrict__ verts, const int* __restrict__ faces, int V, int F,
+                                                     Rec* __restrict__ rec) {
+    record_body<false>(verts, faces, V, F, rec, nullptr);
+}
+__global__ __launch_bounds__(256) void record_kernel_w(const float* __restrict__ verts, const int* __restrict__ faces, int V, int F,
+                                                       Rec* __restrict__ rec, RecW* __restrict__ recw) {
+    record_body<true>(verts, faces, V, F, rec, recw);
 }
 
 __device__ __forceinline__ float clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
@@ -139,16 +176,35 @@ __device__ __forceinline__ float tri_dist2(const Rec& t, float px, float py, flo
     return tri_dist2(t, px, py, pz, rx, ry, rz);
 }
 
+// half the signed solid angle of the triangle seen from p: atan2(determinant, denominator) of van Oosterom & Strackee with a, b, c
+// = corners minus p, positive where p sees the back of the triangle (inside an outward-oriented closed mesh the halves add up to
+// 2 pi).  Plain products in the cross product: two equal vectors give exactly 0.
+__device__ __forceinline__ float tri_half_angle(const Rec& t, const RecW& w, float px, float py, float pz) {
+    const float ax = t.ax - px, ay = t.ay - py, az = t.az - pz;
+    const float bx = w.bx - px, by = w.by - py, bz = w.bz - pz;
+    const float cx = w.cx - px, cy = w.cy - py, cz = w.cz - pz;
+    const float nx = by * cz - bz * cy, ny = bz * cx - bx * cz, nz = bx * cy - by * cx;
+    const float det = w.area * (ax * nx + ay * ny + az * nz);
+    const float la = sqrtf(ax * ax + ay * ay + az * az), lb = sqrtf(bx * bx + by * by + bz * bz), lc = sqrtf(cx * cx + cy * cy + cz * cz);
+    const float ab = ax * bx + ay * by + az * bz, ac = ax * cx + ay * cy + az * cz, bc = bx * cx + by * cy + bz * cz;
+    const float den = la * lb * lc + ab * lc + ac * lb + bc * la;      // the first term is >= +0: a sum of zeros is +0, never -0
+    return atan2f(det, den);
+}
+
 __device__ __forceinline__ unsigned long long md_key(float d2, int idx) {
     return ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned int)idx;
 }
 
-__global__ __launch_bounds__(MD_THREADS) void dist_kernel(const float* __restrict__ points, const Rec* __restrict__ rec, int N, int F,
-                                                          int chunk_faces, unsigned long long* __restrict__ keys) {
-    __shared__ f32x4 tile[MD_TILE * MD_REC / 4];
+template <bool WIND>
+__device__ __forceinline__ void dist_body(const float* __restrict__ points, const Rec* __restrict__ rec, int N, int F, int chunk_faces,
+                                          unsigned long long* __restrict__ keys, const RecW* __restrict__ recw,
+                                          float* __restrict__ wpart) {
+    __shared__ f32x4 tile[MD_TILE * (MD_REC + (WIND ? MD_RECW : 0)) / 4];      // WIND: the RecW of the tile behind its Rec
+    f32x4* const tilew = tile + MD_TILE * MD_REC / 4;
     const int b = blockIdx.z, s = blockIdx.y;
     const float* pb = points + (size_t)b * N * 3;
     float px[MD_P], py[MD_P], pz[MD_P], best[MD_P];
+    float wsum[MD_P];                 // WIND: sum of the half solid angles of this chunk's triangles, in face order
     int bidx[MD_P];
 #pragma unroll
     for (int k = 0; k < MD_P; ++k) {
@@ -156,13 +212,17 @@ __global__ __launch_bounds__(MD_THREADS) void dist_kernel(const float* __restric
         px[k] = pb[(size_t)i * 3], py[k] = pb[(size_t)i * 3 + 1], pz[k] = pb[(size_t)i * 3 + 2];
         best[k] = __uint_as_float(0x7f800000u);
         bidx[k] = 0x7fffffff;
+        wsum[k] = 0.f;
     }
     const int f0 = s * chunk_faces, f1 = min(F, f0 + chunk_faces);
     const f32x4* src = (const f32x4*)(rec + (size_t)b * F);
+    const f32x4* srcw = WIND ? (const f32x4*)(recw + (size_t)b * F) : nullptr;
     for (int base = f0; base < f1; base += MD_TILE) {
         const int n = min(MD_TILE, f1 - base);
         __syncthreads();
         for (int k = threadIdx.x; k < n * (MD_REC / 4); k += MD_THREADS) tile[k] = src[(size_t)base * (MD_REC / 4) + k];
+        if constexpr (WIND)
+            for (int k = threadIdx.x; k < n * (MD_RECW / 4); k += MD_THREADS) tilew[k] = srcw[(size_t)base * (MD_RECW / 4) + k];
         __syncthreads();
         for (int j = 0; j < n; ++j) {
             const f32x4 r0 = tile[j * 4], r1 = tile[j * 4 + 1], r2 = tile[j * 4 + 2], r3 = tile[j * 4 + 3];
@@ -171,10 +231,16 @@ __global__ __launch_bounds__(MD_THREADS) void dist_kernel(const float* __restric
             t.aby = r1.x, t.abz = r1.y, t.acx = r1.z, t.acy = r1.w;
             t.acz = r2.x, t.inv_ab = r2.y, t.inv_ac = r2.z, t.inv_bc = r2.w;
             t.k1 = r3.x, t.k2 = r3.y, t.k3 = r3.z, t.pad = 0.f;
+            RecW w = {};
+            if constexpr (WIND) {
+                const f32x4 w0 = tilew[j * 2], w1 = tilew[j * 2 + 1];
+                w.bx = w0.x, w.by = w0.y, w.bz = w0.z, w.cx = w0.w, w.cy = w1.x, w.cz = w1.y, w.area = w1.z;
+            }
 #pragma unroll
             for (int k = 0; k < MD_P; ++k) {
                 const float q = tri_dist2(t, px[k], py[k], pz[k]);
                 if (q < best[k]) best[k] = q, bidx[k] = base + j;     // ascending faces, strict <: the smallest index keeps a tie
+                if constexpr (WIND) wsum[k] += tri_half_angle(t, w, px[k], py[k], pz[k]);
             }
         }
     }
@@ -184,11 +250,30 @@ __global__ __launch_bounds__(MD_THREADS) void dist_kernel(const float* __restric
         const int i = blockIdx.x * MD_PTS + k * MD_THREADS + (int)threadIdx.x;
         if (i < N) kout[i] = md_key(best[k], bidx[k]);
     }
+    if constexpr (WIND) {
+        float* wout = wpart + ((size_t)s * gridDim.z + b) * N;
+#pragma unroll
+        for (int k = 0; k < MD_P; ++k) {
+            const int i = blockIdx.x * MD_PTS + k * MD_THREADS + (int)threadIdx.x;
+            if (i < N) wout[i] = wsum[k];
+        }
+    }
+}
+__global__ __launch_bounds__(MD_THREADS) void dist_kernel(const float* __restrict__ points, const Rec* __restrict__ rec, int N, int F,
+                                                          int chunk_faces, unsigned long long* __restrict__ keys) {
+    dist_body<false>(points, rec, N, F, chunk_faces, keys, nullptr, nullptr);
+}
+__global__ __launch_bounds__(MD_THREADS) void dist_kernel_w(const float* __restrict__ points, const Rec* __restrict__ rec, int N, int F,
+                                                            int chunk_faces, unsigned long long* __restrict__ keys,
+                                                            const RecW* __restrict__ recw, float* __restrict__ wpart) {
+    dist_body<true>(points, rec, N, F, chunk_faces, keys, recw, wpart);
 }
 
-__global__ __launch_bounds__(256) void finish_kernel(const float* __restrict__ points, const Rec* __restrict__ rec,
-                                                     const unsigned long long* __restrict__ keys, int N, int F, int S,
-                                                     float* __restrict__ dist, int* __restrict__ face_idx, float* __restrict__ closest) {
+template <bool WIND>
+__device__ __forceinline__ void finish_body(const float* __restrict__ points, const Rec* __restrict__ rec,
+                                            const unsigned long long* __restrict__ keys, int N, int F, int S, float* __restrict__ dist,
+                                            int* __restrict__ face_idx, float* __restrict__ closest, const float* __restrict__ wpart,
+                                            float* __restrict__ winding) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
     const int b = blockIdx.y, B = gridDim.y;
@@ -207,6 +292,22 @@ __global__ __launch_bounds__(256) void finish_kernel(const float* __restrict__ p
         tri_dist2(rec[(size_t)b * F + f], px, py, pz, rx, ry, rz);
         closest[o * 3] = px - rx, closest[o * 3 + 1] = py - ry, closest[o * 3 + 2] = pz - rz;
     }
+    if constexpr (WIND) {
+        float w = wpart[o];
+        for (int s = 1; s < S; ++s) w += wpart[((size_t)s * B + b) * N + i];      // ascending chunks: one order, one result
+        winding[o] = w * 0.15915494309189535f;       // sum of half angles / 2 pi = sum of solid angles / 4 pi
+    }
+}
+__global__ __launch_bounds__(256) void finish_kernel(const float* __restrict__ points, const Rec* __restrict__ rec,
+                                                     const unsigned long long* __restrict__ keys, int N, int F, int S,
+                                                     float* __restrict__ dist, int* __restrict__ face_idx, float* __restrict__ closest) {
+    finish_body<false>(points, rec, keys, N, F, S, dist, face_idx, closest, nullptr, nullptr);
+}
+__global__ __launch_bounds__(256) void finish_kernel_w(const float* __restrict__ points, const Rec* __restrict__ rec,
+                                                       const unsigned long long* __restrict__ keys, int N, int F, int S,
+                                                       float* __restrict__ dist, int* __restrict__ face_idx, float* __restrict__ closest,
+                                                       const float* __restrict__ wpart, float* __restrict__ winding) {
+    finish_body<true>(points, rec, keys, N, F, S, dist, face_idx, closest, wpart, winding);
 }
 
 __global__ __launch_bounds__(256) void vertex_kernel(const float* __restrict__ points, const float* __restrict__ verts, int N, int V,
@@ -233,6 +334,46 @@ __global__ __launch_bounds__(256) void vertex_kernel(const float* __restrict__ p
     if (i < N) vert_idx[(size_t)b * N + i] = bi;
 }
 
+// the three launches (+ the nearest-vertex one) of both entry points; `wpart` / `winding` are read by the WIND kernels only
+template <bool WIND>
+int md_run(chore_handle* h, const char* who, const float* points, const float* verts, const int* faces, int B, int N, int V, int F,
+           float* dist, int* face_idx, float* closest, int* vert_idx, float* winding, void* workspace, chore_stream_t stream) {
+    if (!md_shape_ok(B, N, V, F)) CHORE_FAIL(h, CHORE_EINVAL, "%s: unsupported shape B=%d N=%d V=%d F=%d", who, B, N, V, F);
+    if (!points || !verts || !faces || !dist || !workspace || (WIND && !winding)) CHORE_FAIL(h, CHORE_EINVAL, "%s: bad argument", who);
+    hipStream_t s = (hipStream_t)stream;
+    const int S = md_chunks(B, N, F);
+    Rec* rec = (Rec*)workspace;
+    const size_t key_off = md_align((size_t)B * F * sizeof(Rec));
+    unsigned long long* keys = (unsigned long long*)((char*)workspace + key_off);
+    const size_t w_off = key_off + md_align((size_t)S * B * N * sizeof(unsigned long long));     // where the unsigned workspace ends
+    float* wpart = WIND ? (float*)((char*)workspace + w_off) : nullptr;
+    RecW* recw = WIND ? (RecW*)((char*)workspace + w_off + md_align((size_t)S * B * N * sizeof(float))) : nullptr;
+    const dim3 grec((F + 255) / 256, B), gdist((N + MD_PTS - 1) / MD_PTS, S, B), gfin((N + 255) / 256, B);
+    if constexpr (WIND) {
+        hipLaunchKernelGGL(record_kernel_w, grec, dim3(256), 0, s, verts, faces, V, F, rec, recw);
+        CHORE_LAUNCH_CHECK(h, s);
+        hipLaunchKernelGGL(dist_kernel_w, gdist, dim3(MD_THREADS), 0, s, points, (const Rec*)rec, N, F, md_chunk_faces(F, S), keys,
+                           (const RecW*)recw, wpart);
+        CHORE_LAUNCH_CHECK(h, s);
+        hipLaunchKernelGGL(finish_kernel_w, gfin, dim3(256), 0, s, points, (const Rec*)rec, (const unsigned long long*)keys, N, F, S, dist,
+                           face_idx, closest, (const float*)wpart, winding);
+        CHORE_LAUNCH_CHECK(h, s);
+    } else {
+        hipLaunchKernelGGL(record_kernel, grec, dim3(256), 0, s, verts, faces, V, F, rec);
+        CHORE_LAUNCH_CHECK(h, s);
+        hipLaunchKernelGGL(dist_kernel, gdist, dim3(MD_THREADS), 0, s, points, (const Rec*)rec, N, F, md_chunk_faces(F, S), keys);
+        CHORE_LAUNCH_CHECK(h, s);
+        hipLaunchKernelGGL(finish_kernel, gfin, dim3(256), 0, s, points, (const Rec*)rec, (const unsigned long long*)keys, N, F, S, dist,
+                           face_idx, closest);
+        CHORE_LAUNCH_CHECK(h, s);
+    }
+    if (vert_idx) {
+        hipLaunchKernelGGL(vertex_kernel, dim3((N + 255) / 256, B), dim3(256), 0, s, points, verts, N, V, vert_idx);
+        CHORE_LAUNCH_CHECK(h, s);
+    }
+    return CHORE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -246,25 +387,23 @@ size_t chore_mesh_dist_workspace_bytes(int B, int N, int V, int F) {
 int chore_mesh_dist_fwd(chore_handle* h, const float* points, const float* verts, const int* faces, int B, int N, int V, int F,
                         float* dist, int* face_idx, float* closest, int* vert_idx, void* workspace, chore_stream_t stream) {
     CHORE_ENTER(h);
-    if (!md_shape_ok(B, N, V, F)) CHORE_FAIL(h, CHORE_EINVAL, "chore_mesh_dist_fwd: unsupported shape B=%d N=%d V=%d F=%d", B, N, V, F);
-    if (!points || !verts || !faces || !dist || !workspace) CHORE_FAIL(h, CHORE_EINVAL, "chore_mesh_dist_fwd: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    const int S = md_chunks(B, N, F);
-    Rec* rec = (Rec*)workspace;
-    unsigned long long* keys = (unsigned long long*)((char*)workspace + md_align((size_t)B * F * sizeof(Rec)));
-    hipLaunchKernelGGL(record_kernel, dim3((F + 255) / 256, B), dim3(256), 0, s, verts, faces, V, F, rec);
-    CHORE_LAUNCH_CHECK(h, s);
-    hipLaunchKernelGGL(dist_kernel, dim3((N + MD_PTS - 1) / MD_PTS, S, B), dim3(MD_THREADS), 0, s, points, (const Rec*)rec, N, F,
-                       md_chunk_faces(F, S), keys);
-    CHORE_LAUNCH_CHECK(h, s);
-    hipLaunchKernelGGL(finish_kernel, dim3((N + 255) / 256, B), dim3(256), 0, s, points, (const Rec*)rec,
-                       (const unsigned long long*)keys, N, F, S, dist, face_idx, closest);
-    CHORE_LAUNCH_CHECK(h, s);
-    if (vert_idx) {
-        hipLaunchKernelGGL(vertex_kernel, dim3((N + 255) / 256, B), dim3(256), 0, s, points, verts, N, V, vert_idx);
-        CHORE_LAUNCH_CHECK(h, s);
-    }
-    return CHORE_OK;
+    return md_run<false>(h, "chore_mesh_dist_fwd", points, verts, faces, B, N, V, F, dist, face_idx, closest, vert_idx, nullptr, workspace,
+                         stream);
+}
+
+// the unsigned call's workspace + one float per (chunk, image, point) + one RecW per (image, face)
+size_t chore_mesh_sdf_workspace_bytes(int B, int N, int V, int F) {
+    const size_t base = chore_mesh_dist_workspace_bytes(B, N, V, F);
+    if (base == 0) return 0;
+    return base + md_align((size_t)md_chunks(B, N, F) * B * N * sizeof(float)) + md_align((size_t)B * F * sizeof(RecW));
+}
+
+int chore_mesh_sdf_fwd(chore_handle* h, const float* points, const float* verts, const int* faces, int B, int N, int V, int F,
+                       float* dist, int* face_idx, float* closest, int* vert_idx, float* winding, void* workspace,
+                       chore_stream_t stream) {
+    CHORE_ENTER(h);
+    return md_run<true>(h, "chore_mesh_sdf_fwd", points, verts, faces, B, N, V, F, dist, face_idx, closest, vert_idx, winding, workspace,
+                        stream);
 }
 
 }  // extern "C"

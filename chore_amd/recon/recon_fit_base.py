@@ -8,6 +8,7 @@ the same.  Heavy steps run in libchore_hip.so: the field queries (chore_query_fw
 (chore_smpl_lbs_*) and the SO(3) projection (chore_so3_project_*); the remaining terms are a few
 reductions over (B,N) tensors expressed with torch ops on the device.
 """
+import json
 import os
 import threading
 import pickle as pkl
@@ -380,6 +381,47 @@ class ReconFitterBase:
             write_ply(of, obj_verts[i], self.scan.f)
             pkl.dump({"rot": rot[i], "trans": obj_t[i].detach().cpu().numpy(), "scale": obj_s[i].detach().cpu().numpy()},
                      open(of.replace(".ply", ".pkl"), "wb"))
+        if self.REPORT_PENETRATION:             # of the very meshes written above; draws no random numbers
+            if smpl.faces is None:
+                raise RuntimeError("REPORT_PENETRATION needs the body model's faces")
+            dev = self.device
+            rep = self._penetration_of(torch.as_tensor(verts, device=dev), smpl.faces, torch.as_tensor(obj_verts, device=dev))
+            rep = {k: None if v is None else {n: t.cpu().tolist() for n, t in v.items()} for k, v in rep.items()}
+            for i, sf in enumerate(smpl_files):
+                frame = {k: None if v is None else {n: x[i] for n, x in v.items()} for k, v in rep.items()}
+                with open(sf.replace(".smpl.ply", ".penetration.json"), "w") as f:
+                    json.dump(frame, f, indent=1)
+
+    # ---- how far the fitted meshes sit inside each other (recon/eval/penetration.py) ------------------------
+    # Not in the reference.  An exact measure, independent of the interpenetration term, of what that term is there to reduce:
+    # vertices of one mesh inside the other by winding number, depth by the exact distance to the other's surface.
+    # True: save_outputs also writes k{test_id}.penetration.json (one frame's penetration_report) next to the PLY files.
+    # The fit itself never reads it: no fitted bit changes.
+    REPORT_PENETRATION = False
+
+    def _penetration_of(self, smpl_verts, smpl_faces, obj_verts):
+        from .eval.penetration import is_closed, penetration
+        if self.scan_faces is None:
+            raise RuntimeError("penetration_report needs the object template mesh (scan_verts / scan_faces)")
+        if getattr(self, "_scan_closed", None) is None or self._scan_closed[0] is not self.scan_faces:
+            self._scan_closed = (self.scan_faces, is_closed(self.scan_faces))          # host, once per template
+        with torch.no_grad():
+            out = {"object_in_body": penetration(smpl_verts, smpl_faces, obj_verts), "body_in_object": None}
+            if self._scan_closed[1]:
+                out["body_in_object"] = penetration(obj_verts, self.scan_faces, smpl_verts)
+        return out
+
+    def penetration_report(self, smpl_verts, smpl_faces, obj_R, obj_t, obj_s):
+        """the arguments of compute_collision_loss (obj_R: rotation matrices) -> {"object_in_body": vertices of the transformed
+        template inside the body, "body_in_object": body vertices inside the template, or None when the template is not a
+        closed mesh (is_closed)}; each a dict of per-frame device tensors count / frac / max_depth / mean_depth
+        (recon/eval/penetration.py).  The body mesh is taken to be closed, as SMPL's is.  No gradient."""
+        if self.scan_verts is None:
+            raise RuntimeError("penetration_report needs the object template mesh (scan_verts / scan_faces)")
+        with torch.no_grad():
+            scan = self.scan_verts.unsqueeze(0).expand(obj_R.shape[0], -1, -1)
+            verts = self.transform_obj_verts(scan, obj_R.detach(), obj_t.detach(), obj_s.detach())
+        return self._penetration_of(smpl_verts.detach(), smpl_faces, verts)
 
     # ---- SO(3) ------------------------------------------------------------------------------------
     @staticmethod

@@ -836,6 +836,19 @@ int chore_fit_rot_noise(chore_handle* h, const float* rot, const float* noise, i
 size_t chore_mesh_dist_workspace_bytes(int B, int N, int V, int F);
 int chore_mesh_dist_fwd(chore_handle* h, const float* points, const float* verts, const int* faces, int B, int N, int V, int F,
                         float* dist, int* face_idx, float* closest, int* vert_idx, void* workspace, chore_stream_t stream);
+/* chore_mesh_dist_fwd plus the side of the surface, forward only: the same dist / face_idx / closest / vert_idx, bit for bit, and
+ *   winding (B,N)     the generalized winding number of mesh b about the point (Jacobson et al. 2013): the sum over all F
+ *                     triangles of the signed solid angle 2 atan2(a.(b x c), |a||b||c| + (a.b)|c| + (a.c)|b| + (b.c)|a|), a, b, c
+ *                     = corners minus the point, divided by 4 pi.  +1 inside a closed mesh whose faces are oriented outward, -1
+ *                     where they are oriented inward, 0 outside, fractional about an open mesh; required
+ * A triangle of zero area (repeated index, exactly parallel edges) and a point on one of a triangle's corners contribute
+ * exactly 0; a point ON the surface gets a finite value whose sign is not specified.  fp32, summed in a fixed order without
+ * atomics: the same shapes and inputs give the same bits.  chore_mesh_sdf_workspace_bytes is chore_mesh_dist_workspace_bytes
+ * plus the partial sums (0 = unsupported shape); the call can be captured into a graph. */
+size_t chore_mesh_sdf_workspace_bytes(int B, int N, int V, int F);
+int chore_mesh_sdf_fwd(chore_handle* h, const float* points, const float* verts, const int* faces, int B, int N, int V, int F,
+                       float* dist, int* face_idx, float* closest, int* vert_idx, float* winding, void* workspace,
+                       chore_stream_t stream);
 
 /* debug aid: with CHORE_NAN_CHECK=1 in the environment chore_query_fwd / chore_query_bwd_points scan their inputs and
  * outputs for non-finite values (extra launches on the caller's stream); out32[0..15] = counts per site (0 points, 1-4 the
