@@ -7,6 +7,7 @@
 //   K_ij = (H_ij - H_ji) / (d_i sigma_i + d_j sigma_j),   dL/dM = U D K V^T
 // which is the derivative of the projection itself (it does not contain the 1/(sigma_i^2 - sigma_j^2)
 // terms of a generic SVD backward, so it stays finite for repeated singular values).
+// Inputs of rank <= 1 are outside the contract: the result is then not a rotation (svd3.h completes only a vanishing THIRD column).
 #include "common.h"
 #include "svd3.h"
 

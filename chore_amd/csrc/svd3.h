@@ -1,5 +1,6 @@
 // svd3.h -- 3x3 singular value decomposition in fp64 (one thread): cyclic Jacobi on M^T M -> V, sigma; U = M V / sigma.
 // Shared by the SO(3) projection of the fit (so3.hip) and the Procrustes alignment of the evaluation (eval_metrics.hip).
+// Inputs of rank <= 1 (the zero matrix included) are outside the contract: U is then not orthogonal, so U D V^T is not a rotation.
 #pragma once
 #include <hip/hip_runtime.h>
 
