@@ -214,6 +214,8 @@ SIGNATURES = {
     "chore_mesh_dist_fwd": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 6),
     "chore_mesh_sdf_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "chore_mesh_sdf_fwd": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 7),
+    "chore_mesh_dist_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "chore_mesh_dist_bwd": (c_int, [c_void_p] * 8 + [c_int] * 4 + [c_void_p] * 4),
     "chore_contact_workspace_bytes":(c_size_t, [c_int, c_int, c_int, c_int]),
     "chore_contact_fwd": (c_int, [c_void_p] * 7 + [c_int] * 4 + [c_float, c_void_p, c_void_p, c_void_p]),
     "chore_contact_bwd": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 5),

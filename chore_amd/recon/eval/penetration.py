@@ -3,7 +3,10 @@
 
 A vertex of B is inside A when |generalized winding number of A about it| > 0.5 (chore_amd.preprocess.mesh_distance,
 `inside`); its depth is the exact distance to A's surface.  Both come from ONE mesh_distance call over the whole batch; no
-host loop over frames.  Only A, the mesh that is tested against, has to be closed (`is_closed`): B's faces are not used."""
+host loop over frames.  Only A, the mesh that is tested against, has to be closed (`is_closed`): B's faces are not used.
+
+`penetration` is the report (no gradient); `penetration_loss` is the same quantity as one differentiable number per frame, the
+opt-in term of the joint fit (ReconFitterBase.PENETRATION_TERM)."""
 import numpy as np
 import torch
 
@@ -38,3 +41,14 @@ def penetration(verts_a, faces_a, verts_b, faces_b=None):
     count = inside.sum(1)
     return {"count": count, "frac": count.to(torch.float32) / vb.shape[1], "max_depth": depth.max(1).values,
             "mean_depth": depth.sum(1) / count.clamp(min=1).to(torch.float32)}
+
+
+def penetration_loss(verts_a, faces_a, verts_b):
+    """the mean over ALL vertices of B of their depth inside A, per frame: sum_i inside_i dist_i / Vb -> (B,) float32 on the
+    device (unbatched input: (1,)), = frac * mean_depth of penetration().  Differentiable in both vertex sets through the
+    exact distance (chore_mesh_dist_bwd); `inside` is a constant of the step (the winding number is not differentiated).
+    One mesh_distance call; nothing is read on the host, so a step that holds it can be captured into a graph."""
+    va = verts_a[None] if verts_a.dim() == 2 else verts_a
+    vb = verts_b[None] if verts_b.dim() == 2 else verts_b
+    dist, inside = mesh_distance(vb, va, faces_a, ("dist", "inside"))
+    return torch.where(inside, dist, torch.zeros_like(dist)).sum(1) / vb.shape[1]

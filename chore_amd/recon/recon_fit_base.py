@@ -399,17 +399,44 @@ class ReconFitterBase:
     # The fit itself never reads it: no fitted bit changes.
     REPORT_PENETRATION = False
 
-    def _penetration_of(self, smpl_verts, smpl_faces, obj_verts):
-        from .eval.penetration import is_closed, penetration
-        if self.scan_faces is None:
-            raise RuntimeError("penetration_report needs the object template mesh (scan_verts / scan_faces)")
+    # True: forward_step(..., "joint") adds loss_dict["pen"] = compute_penetration_loss after "collide" (when there is a
+    # template mesh).  An exact, differentiable restatement of what the report prints, weighted by get_loss_weights()["pen"].
+    # False (the default): nothing is computed, no key appears, no fitted bit changes.
+    PENETRATION_TERM = False
+
+    def _template_closed(self):
+        """is the template a closed mesh (is_closed)?  Checked on the host once per template -- before any step is recorded"""
+        from .eval.penetration import is_closed
         if getattr(self, "_scan_closed", None) is None or self._scan_closed[0] is not self.scan_faces:
             self._scan_closed = (self.scan_faces, is_closed(self.scan_faces))          # host, once per template
+        return self._scan_closed[1]
+
+    def _penetration_of(self, smpl_verts, smpl_faces, obj_verts):
+        from .eval.penetration import penetration
+        if self.scan_faces is None:
+            raise RuntimeError("penetration_report needs the object template mesh (scan_verts / scan_faces)")
+        closed = self._template_closed()
         with torch.no_grad():
             out = {"object_in_body": penetration(smpl_verts, smpl_faces, obj_verts), "body_in_object": None}
-            if self._scan_closed[1]:
+            if closed:
                 out["body_in_object"] = penetration(obj_verts, self.scan_faces, smpl_verts)
         return out
+
+    def compute_penetration_loss(self, smpl_verts, smpl_faces, obj_R, obj_t, obj_s):
+        """the arguments of compute_collision_loss -> the mean over the frames of penetration_loss(body, smpl_faces, template)
+        [template vertices inside the body] + penetration_loss(template, scan_faces, body) [body vertices inside the template;
+        only when the template is a closed mesh, _penetration_of's rule]: per direction frac * mean_depth of
+        penetration_report, in metres.  Differentiable in the body and in obj_R / obj_t / obj_s (recon/eval/penetration.py)."""
+        from .eval.penetration import penetration_loss
+        if self.scan_verts is None or self.scan_faces is None:
+            raise RuntimeError("compute_penetration_loss needs the object template mesh (scan_verts / scan_faces)")
+        closed = self._template_closed()
+        scan = self.scan_verts.unsqueeze(0).expand(obj_R.shape[0], -1, -1)
+        verts = self.transform_obj_verts(scan, obj_R, obj_t, obj_s)
+        loss = penetration_loss(smpl_verts, smpl_faces, verts)
+        if closed:
+            loss = loss + penetration_loss(verts, self.scan_faces, smpl_verts)
+        return loss.mean()
 
     def penetration_report(self, smpl_verts, smpl_faces, obj_R, obj_t, obj_s):
         """the arguments of compute_collision_loss (obj_R: rotation matrices) -> {"object_in_body": vertices of the transformed

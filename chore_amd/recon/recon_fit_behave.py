@@ -202,7 +202,10 @@ class ReconFitterBehave(ReconFitterBase):
     def get_loss_weights(self):
         w = {"beta": 1.0, "pose": 1e-5, "hand": 1e-5, "j2d": 0.3 ** 2, "object": 30.0 ** 2, "part": 0.05 ** 2,
              "contact": 30.0 ** 2, "scale": 10.0 ** 2, "df_h": 30.0 ** 2, "smplz": 30 ** 2, "mask": 0.003 ** 2,
-             "ocent": 15 ** 2, "collide": 3 ** 2, "pinit": 5 ** 2, "rot": 10.0 ** 2, "trans": 10.0 ** 2}
+             "ocent": 15 ** 2, "collide": 3 ** 2, "pinit": 5 ** 2, "rot": 10.0 ** 2, "trans": 10.0 ** 2,
+             # "pen" (PENETRATION_TERM, not in the reference): the coefficient this table gives the two other terms that are a
+             # mean of distances in metres ("object", "df_h").  Not tuned.
+             "pen": 30.0 ** 2}
         return {k: (lambda cst, it, c=c: c * cst / (1 + it)) for k, c in w.items()}
 
     # ---- the whole chain ------------------------------------------------------------------------------
@@ -759,6 +762,8 @@ class ReconFitterBehave(ReconFitterBase):
             self.compute_contact_loss(df_hum_o, df_obj_h, object, smpl_verts, loss_dict, part_o=part_o)
             if self.scan_faces is not None:
                 loss_dict["collide"] = self.compute_collision_loss(smpl_verts, smpl.faces, R, obj_t, obj_s)
+                if self.PENETRATION_TERM:      # opt-in: the exact depth the penetration report prints, as a term
+                    loss_dict["pen"] = self.compute_penetration_loss(smpl_verts, smpl.faces, R, obj_t, obj_s)
         return loss_dict
 
     def optimize_smpl_object(self, model, data_dict, obj_iter=20, joint_iter=10, steps_per_iter=10, sil_iter=50,
@@ -801,7 +806,8 @@ class ReconFitterBehave(ReconFitterBase):
         if obj_R.is_cuda and (sil is None or hasattr(sil, "load_from")):
             slot = self._slot("object", tuple(obj_R.shape), tuple(data_dict["objects"].shape), tuple(body.shape), str(obj_R.device),
                               self._maps_key(model), obj_iter, joint_iter, steps_per_iter, sil_iter, max_iter,
-                              None if sil is None else (type(sil).__name__, tuple(getattr(sil, "image_ref", torch.empty(0)).shape)))
+                              None if sil is None else (type(sil).__name__, tuple(getattr(sil, "image_ref", torch.empty(0)).shape)),
+                              bool(self.PENETRATION_TERM))     # kept graphs of one setting are not replayed under the other
         if slot is None:
             self._optimize_object(model, split, data_dict, None, obj_R, obj_t, obj_s, obj_iter, joint_iter, steps_per_iter,
                                   sil_iter, max_iter)
@@ -837,6 +843,8 @@ class ReconFitterBehave(ReconFitterBase):
                          max_iter):
         """the three phases on the given parameter tensors (the caller's, or a slot's private ones)"""
         wd = self.get_loss_weights()
+        if self.PENETRATION_TERM and self.scan_faces is not None:
+            self._template_closed()         # the host check of the template, before any step is recorded
         prev = torch.tensor(300.0, device=self.device)
         if slot is not None:
             prev = slot.bind("prev", prev)

@@ -30,4 +30,6 @@ class ReconFitterCoco(ReconFitterBehave):
         w = {"beta": 10.0 ** 0, "pose": 10.0 ** -5, "hand": 10.0 ** -5, "j2d": 0.8 ** 2, "object": 90.0 ** 2,
              "part": 0.05 ** 2, "contact": 150.0 ** 2, "scale": 2.0 ** 2, "df_h": 30.0 ** 2, "smplz": 30 ** 2,
              "pinit": 10 ** 2, "ocent": 30 ** 2, "mask": 0.3 ** 2, "collide": 15 ** 2, "trans": 10.0 ** 2}
+        if self.PENETRATION_TERM:       # not in the reference, whose table this is key for key: the opt-in term's coefficient as
+            w["pen"] = 30.0 ** 2        # in recon_fit_behave.py (that of a mean of distances in metres there), not tuned
         return {k: (lambda cst, it, c=c: c * cst / (1 + it)) for k, c in w.items()}

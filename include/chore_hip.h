@@ -821,7 +821,7 @@ int chore_fit_rot_noise(chore_handle* h, const float* rot, const float* noise, i
                         float* out, chore_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Exact unsigned distance from points to a triangle mesh, forward only  (what the training-data sampler takes from
+ * Exact unsigned distance from points to a triangle mesh; its gradient is chore_mesh_dist_bwd below  (what the training-data sampler takes from
  * np.abs(igl.signed_distance(P, V, F)[0]), its I and C, and from trimesh.proximity.ProximityQuery(mesh).vertex(P)[1]:
  * preprocess/boundary_sampler.py:45-64).  points (B,N,3), verts (B,V,3) fp32, faces (F,3) int32 shared by the batch.
  *   dist (B,N)        Euclidean distance to the triangle SURFACE of mesh b: the minimum over all F triangles (interior, edge
@@ -836,7 +836,7 @@ int chore_fit_rot_noise(chore_handle* h, const float* rot, const float* noise, i
 size_t chore_mesh_dist_workspace_bytes(int B, int N, int V, int F);
 int chore_mesh_dist_fwd(chore_handle* h, const float* points, const float* verts, const int* faces, int B, int N, int V, int F,
                         float* dist, int* face_idx, float* closest, int* vert_idx, void* workspace, chore_stream_t stream);
-/* chore_mesh_dist_fwd plus the side of the surface, forward only: the same dist / face_idx / closest / vert_idx, bit for bit, and
+/* chore_mesh_dist_fwd plus the side of the surface (no gradient through the winding number): the same dist / face_idx / closest / vert_idx, bit for bit, and
  *   winding (B,N)     the generalized winding number of mesh b about the point (Jacobson et al. 2013): the sum over all F
  *                     triangles of the signed solid angle 2 atan2(a.(b x c), |a||b||c| + (a.b)|c| + (a.c)|b| + (b.c)|a|), a, b, c
  *                     = corners minus the point, divided by 4 pi.  +1 inside a closed mesh whose faces are oriented outward, -1
@@ -849,6 +849,28 @@ size_t chore_mesh_sdf_workspace_bytes(int B, int N, int V, int F);
 int chore_mesh_sdf_fwd(chore_handle* h, const float* points, const float* verts, const int* faces, int B, int N, int V, int F,
                        float* dist, int* face_idx, float* closest, int* vert_idx, float* winding, void* workspace,
                        chore_stream_t stream);
+/* The gradient of dist with respect to the points and the mesh vertices.  face_idx (B,N), closest (B,N,3) and dist (B,N) are
+ * the forward's outputs for these very points / verts / faces, g_dist (B,N) the upstream gradient of dist.  `closest` is
+ * accepted and NOT read (NULL is allowed): c is formed again in fp64 from the saved winner, because the fp32 rounding of a
+ * stored closest point, eps |c|, would enter the direction as eps |c| / dist.  With r = p - c and dist in the sense of |r|:
+ *   dpoints (B,N,3)   dpoints[b,n] = g r / |r|, and 0 where dist == 0; NULL = not wanted
+ *   dverts (B,V,3)    dverts[b,v] = the sum over all (n,k) with faces[face_idx[b,n]][k] == v of -b_k dpoints[b,n]; NULL = not wanted
+ * b_k are the barycentric coordinates of the closest point in its triangle, recomputed here for the saved winner face_idx (the
+ * closest point of p on that triangle by its Voronoi regions, in fp64: a point beyond a corner gives the other two corners
+ * exactly 0; in the vertex, edge and interior regions alike the derivative with respect to corner k is -b_k r / dist, dist
+ * being a minimum over b), clamped to [0,1] with b_0 = 1 - b_1 - b_2.  A vertex that no winning triangle references gets exactly 0.  A zero-area winning triangle
+ * gets finite weights that sum to 1 -- nothing more is promised there: the distance is not differentiable in the corners of a
+ * degenerate triangle; nor is it where two triangles with different closest points tie (the gradient of the winner is given).
+ * A NULL output skips its kernels and does not change the other's bits (as chore_contact_bwd).  The sums over the points are
+ * formed per vertex in ascending point order, in chunks whose number depends on the shapes only, without atomics: the same shapes
+ * and inputs give the same bits.  chore_mesh_dist_bwd_workspace_bytes depends on the shapes only (0 = unsupported shape); nothing
+ * is allocated and no device value is read by the host, so the call can be captured into a graph.  The gradient of the sign-mode
+ * "inside" signed distance is this one with g negated where the point is inside (the sign is locally constant); the winding
+ * number itself is not differentiated. */
+size_t chore_mesh_dist_bwd_workspace_bytes(int B, int N, int V, int F);
+int chore_mesh_dist_bwd(chore_handle* h, const float* points, const float* verts, const int* faces, const int* face_idx,
+                        const float* closest, const float* dist, const float* g_dist, int B, int N, int V, int F, float* dpoints,
+                        float* dverts, void* workspace, chore_stream_t stream);
 
 /* debug aid: with CHORE_NAN_CHECK=1 in the environment chore_query_fwd / chore_query_bwd_points scan their inputs and
  * outputs for non-finite values (extra launches on the caller's stream); out32[0..15] = counts per site (0 points, 1-4 the
