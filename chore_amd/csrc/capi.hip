@@ -3,13 +3,6 @@
 #include <cstdlib>
 #include <cstring>
 
-int launch_query_fwd_f32_bf16maps(chore_handle* h, const QueryArgs& a, hipStream_t s);
-int launch_query_fwd_x3(chore_handle* h, int dtype, const QueryArgs& a, hipStream_t s);
-int launch_query_bwd_x3(chore_handle* h, int dtype, const QueryArgs& a, hipStream_t s);
-size_t heads_arena_bytes();
-int launch_query_bwd_f32_bf16maps(chore_handle* h, const QueryArgs& a, hipStream_t s);
-int launch_sample_features(chore_handle* h, int dtype, const QueryArgs& a, float* features, float* nxy, hipStream_t s);
-
 static thread_local std::string g_noh_err;
 
 static const void* find_desc(const chore_weight_desc* d, int n, const std::string& name, int64_t numel,
@@ -199,6 +192,26 @@ static int fill_query_args(chore_handle* h, QueryArgs& a, const float* points, c
     return CHORE_OK;
 }
 
+// the plan of a call from its filled arguments, under this process's switches
+static QueryPlan plan_of(int op, int dtype, bool x3, const QueryArgs& a, bool has_workspace = false, bool have_forward = false) {
+    int live = 0;
+    for (int i = 0; i < HEAD_NUM; ++i) live |= (a.g[i] != nullptr) << i;
+    return query_plan(op, dtype, x3, a.B, a.N, a.FH, a.FW, live, has_workspace, have_forward, query_switches());
+}
+
+int chore_query_plan(int op, int dtype, int B, int N, int FH, int FW, int live_mask, int flags, int switches, int* out, int n) {
+    const bool x3 = query_x3(dtype);
+    if (op < QUERY_FWD || op > QUERY_BWD_TRAIN || (dtype != CHORE_F32 && dtype != CHORE_BF16 && dtype != CHORE_F16) || B <= 0 || N <= 0 ||
+        FH < 2 || FW < 2 || !out || n <= 0 || query_plan_refuses(op, dtype, x3, flags & 2))
+        return CHORE_EINVAL;
+    const QueryPlan p = query_plan(op, dtype, x3, B, N, FH, FW, live_mask & 15, flags & 1, flags & 2, switches < 0 ? query_switches() : switches);
+    const int v[9] = {p.family, p.ncb, p.waves, p.train | p.staged << 1 | p.x3 << 2 | p.surf << 3 | p.one << 4, p.one_head, p.pts, p.threads,
+                      p.sort, p.dtype};
+    const int k = n < 9 ? n : 9;
+    for (int i = 0; i < k; ++i) out[i] = v[i];
+    return k;
+}
+
 size_t chore_query_fwd_workspace_bytes(int B, int N) {
     if (B <= 0 || N <= 0) return 0;
     return (size_t)B * query_sort_ints(N) * sizeof(int);
@@ -229,13 +242,12 @@ int chore_query_fwd_ws(chore_handle* h, const float* points, const float* crop_c
         nan_scan(points, (size_t)B * N * 3, 0, (hipStream_t)stream);
         if (dtype == CHORE_F32) { nan_scan((const float*)feat, (size_t)B * FH * FW * 256, 5, (hipStream_t)stream); nan_scan((const float*)tmpx, (size_t)B * TH * TW * 64, 6, (hipStream_t)stream); }
     }
-    // sorted order: asked for by passing a workspace; large queries on the fp16 x 3 split kernel (the only one that reads QueryArgs::perm)
-    if (workspace && x3 && N >= 8192 && !getenv("CHORE_QUERY_X3_NOSPLIT") && query_sort_covers(a)) {
+    const QueryPlan p = plan_of(QUERY_FWD, dtype, x3, a, workspace != nullptr);
+    if (p.sort) {     // sorted order (asked for by passing a workspace)
         if ((rc = launch_query_sort(h, a, (int*)workspace, (hipStream_t)stream))) return rc;
         a.perm = (const int*)workspace;
     }
-    rc = x3 ? launch_query_fwd_x3(h, dtype, a, (hipStream_t)stream)
-            : (dtype == CHORE_F32 ? launch_query_fwd_f32(h, a, (hipStream_t)stream) : launch_query_fwd_f32_bf16maps(h, a, (hipStream_t)stream));
+    rc = launch_query_fwd(h, p, a, (hipStream_t)stream);
     if (nan_check_on()) {
         if (df) nan_scan(df, (size_t)B * 2 * N, 1, (hipStream_t)stream);
         if (pca) nan_scan(pca, (size_t)B * 9 * N, 2, (hipStream_t)stream);
@@ -280,14 +292,10 @@ int chore_query_bwd_points(chore_handle* h, const float* points, const float* cr
         if (g_pca) nan_scan(g_pca, (size_t)B * 9 * N, 10, (hipStream_t)stream);
         if (g_parts) nan_scan(g_parts, (size_t)B * 14 * N, 11, (hipStream_t)stream);
         if (g_centers) nan_scan(g_centers, (size_t)B * 6 * N, 12, (hipStream_t)stream);
-        rc = x3 ? launch_query_bwd_x3(h, dtype, a, (hipStream_t)stream)
-                : (dtype == CHORE_F32 ? launch_query_bwd_f32(h, a, (hipStream_t)stream) : launch_query_bwd_f32_bf16maps(h, a, (hipStream_t)stream));
-        nan_scan(dpoints, (size_t)B * N * 3, 13, (hipStream_t)stream);
-        return rc;
     }
-    if (x3) return launch_query_bwd_x3(h, dtype, a, (hipStream_t)stream);
-    return dtype == CHORE_F32 ? launch_query_bwd_f32(h, a, (hipStream_t)stream)
-                              : launch_query_bwd_f32_bf16maps(h, a, (hipStream_t)stream);
+    rc = launch_query_bwd(h, plan_of(QUERY_BWD_POINTS, dtype, x3, a), a, (hipStream_t)stream);
+    if (nan_check_on()) nan_scan(dpoints, (size_t)B * N * 3, 13, (hipStream_t)stream);
+    return rc;
 }
 
 int chore_gen_surface_step_fused(chore_handle* h, const float* points, const float* crop_center, int B, int N, const void* feat,
@@ -295,8 +303,8 @@ int chore_gen_surface_step_fused(chore_handle* h, const float* points, const flo
                                  const float* cam6_host, int k, float thr, float* out_points, chore_stream_t stream) {
     CHORE_ENTER(h);
     if (!out_points || (k != 0 && k != 1)) CHORE_FAIL(h, CHORE_EINVAL, "chore_gen_surface_step_fused: bad argument");
-    if (!query_x3(dtype))
-        CHORE_FAIL(h, CHORE_EINVAL, "chore_gen_surface_step_fused: needs the fp16 x 3 heads (CHORE_F16X3, or CHORE_HEADS_X3 with the maps' type)");
+    const bool x3 = query_x3(dtype);
+    if (const char* why = query_plan_refuses(QUERY_SURFACE_STEP, dtype, x3, false)) CHORE_FAIL(h, CHORE_EINVAL, "chore_gen_surface_step_fused: %s", why);
     QueryArgs a;
     int rc = fill_query_args(h, a, points, crop_center, B, N, feat, FH, FW, tmpx, TH, TW, dtype, heads_arena, cam6_host);
     if (rc) return rc;
@@ -305,7 +313,7 @@ int chore_gen_surface_step_fused(chore_handle* h, const float* points, const flo
     a.dpoints = out_points;
     a.surf_k = k;
     a.surf_thr = thr;
-    return launch_query_surface_step(h, dtype, a, (hipStream_t)stream);
+    return launch_query_bwd(h, plan_of(QUERY_SURFACE_STEP, dtype, x3, a), a, (hipStream_t)stream);
 }
 
 size_t chore_query_train_bytes(int B, int N) {
@@ -335,16 +343,14 @@ int chore_query_fwd_train(chore_handle* h, const float* points, const float* cro
     if (!df || !pca || !parts || !centers || !staging) CHORE_FAIL(h, CHORE_EINVAL, "chore_query_fwd_train: null output");
     QueryArgs a;
     const bool x3 = query_x3(dtype);
-    // checked AFTER the heads flag is stripped: CHORE_F16 | CHORE_HEADS_X3 must not get past (the launchers below read fp32 or bf16)
-    if (dtype != CHORE_F32 && dtype != CHORE_BF16)
-        CHORE_FAIL(h, CHORE_EINVAL, "chore_query_fwd_train: maps must be CHORE_F32 or CHORE_BF16 (fp16 maps are an inference mode)");
+    if (const char* why = query_plan_refuses(QUERY_FWD_TRAIN, dtype, x3, true)) CHORE_FAIL(h, CHORE_EINVAL, "chore_query_fwd_train: %s", why);
     int rc = fill_query_args(h, a, points, crop_center, B, N, feat, FH, FW, tmpx, TH, TW, dtype, heads_arena,
                              cam6_host);
     if (rc) return rc;
     a.out[0] = df; a.out[1] = parts; a.out[2] = pca; a.out[3] = centers;
     a.in_img = in_img;
     train_staging(a, staging);
-    return launch_query_fwd_train(h, dtype, a, (hipStream_t)stream, x3);
+    return launch_query_fwd(h, plan_of(QUERY_FWD_TRAIN, dtype, x3, a), a, (hipStream_t)stream);
 }
 
 int chore_query_bwd_train(chore_handle* h, const float* points, const float* crop_center, int B, int N,
@@ -356,17 +362,14 @@ int chore_query_bwd_train(chore_handle* h, const float* points, const float* cro
     if (!staging) CHORE_FAIL(h, CHORE_EINVAL, "chore_query_bwd_train: null staging");
     QueryArgs a;
     const bool x3 = query_x3(dtype);
-    // checked AFTER the heads flag is stripped: CHORE_F16 | CHORE_HEADS_X3 must not get past (the launchers below read fp32 or bf16)
-    if (dtype != CHORE_F32 && dtype != CHORE_BF16)
-        CHORE_FAIL(h, CHORE_EINVAL, "chore_query_bwd_train: maps must be CHORE_F32 or CHORE_BF16 (fp16 maps are an inference mode)");
-    if (x3 && !have_forward) CHORE_FAIL(h, CHORE_EINVAL, "chore_query_bwd_train: the fp16 x 3 heads need the staged forward");
+    if (const char* why = query_plan_refuses(QUERY_BWD_TRAIN, dtype, x3, have_forward)) CHORE_FAIL(h, CHORE_EINVAL, "chore_query_bwd_train: %s", why);
     int rc = fill_query_args(h, a, points, crop_center, B, N, feat, FH, FW, tmpx, TH, TW, dtype, heads_arena,
                              cam6_host);
     if (rc) return rc;
     a.g[0] = g_df; a.g[1] = g_parts; a.g[2] = g_pca; a.g[3] = g_centers;
     a.dpoints = dpoints;
     train_staging(a, staging);
-    return launch_query_bwd_train(h, dtype, a, (hipStream_t)stream, have_forward, x3);
+    return launch_query_bwd(h, plan_of(QUERY_BWD_TRAIN, dtype, x3, a, false, have_forward), a, (hipStream_t)stream);
 }
 
 int chore_scatter_features(chore_handle* h, const float* points, const float* crop_center, int B, int N, int FH, int FW,

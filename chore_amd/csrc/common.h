@@ -8,6 +8,7 @@
 #include <vector>
 #include <unordered_map>
 #include "../../include/chore_hip.h"
+#include "query_plan.h"
 
 struct chore_handle {
     int device = 0;
@@ -278,15 +279,14 @@ __host__ __device__ static inline size_t scatter_sort_ints(int N) { return 4 * (
 
 // launchers implemented in the .hip files
 int launch_heads_pack_f32(chore_handle* h, const HeadsRaw& raw, float* arena, hipStream_t s);
-int launch_query_fwd_f32(chore_handle* h, const QueryArgs& a, hipStream_t s);
-int launch_query_bwd_f32(chore_handle* h, const QueryArgs& a, hipStream_t s);
-int launch_query_surface_step(chore_handle* h, int dtype, const QueryArgs& a, hipStream_t s);
-int launch_query_bwd_train(chore_handle* h, int dtype, const QueryArgs& a, hipStream_t s, int staged = 0, int x3 = 0);
-int launch_query_fwd_train(chore_handle* h, int dtype, const QueryArgs& a, hipStream_t s, int x3 = 0);
+// the query kernels (query_fwd.hip, query_bwd.hip): query_plan() decides, these launch the plan's instantiation or fail
+int launch_query_fwd(chore_handle* h, const QueryPlan& p, const QueryArgs& a, hipStream_t s);
+int launch_query_bwd(chore_handle* h, const QueryPlan& p, const QueryArgs& a, hipStream_t s);
+int launch_sample_features(chore_handle* h, int dtype, const QueryArgs& a, float* features, float* nxy, hipStream_t s);
+size_t heads_arena_bytes();
 int launch_scatter_features(chore_handle* h, const QueryArgs& a, const float* dX, float* dfeat, float* dtmpx,
                             int accumulate, hipStream_t s);
 // the points of every image ordered by the 8 x 8-texel tile of the feature map their sample falls into: perm [B][N] at the
-// start of `work` (B x query_sort_ints(N) ints in all: the permutations, then the images' sort regions); false = shape not covered
+// start of `work` (B x query_sort_ints(N) ints in all: the permutations, then the images' sort regions); covered: QueryPlan::sort
 __host__ __device__ static inline size_t query_sort_ints(int N) { return (size_t)N + scatter_sort_ints(N); }
-bool query_sort_covers(const QueryArgs& a);
 int launch_query_sort(chore_handle* h, const QueryArgs& a, int* work, hipStream_t s);

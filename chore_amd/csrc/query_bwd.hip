@@ -9,7 +9,6 @@
 // MFMA scheme (D fragment of one GEMM = B fragment of the next).  The four heads' contributions to
 // d(323-vector) are reduced through LDS in a fixed order, so the result is deterministic.
 #include "heads_x3.h"
-#include <cstdlib>
 
 template <int PTS>
 struct QueryBwdSmemT {
@@ -460,110 +459,43 @@ __global__ __launch_bounds__(NW * 64, 1) void query_bwd_f32_kernel(QueryArgs a) 
     }
 }
 
-template <typename T, bool TRAIN, int NCB, bool X3 = false>
-static int launch_query_bwd_n(chore_handle* h, const QueryArgs& a, hipStream_t s) {
-    constexpr int PTS = 32 * NCB;
-    const size_t smem = sizeof(QueryBwdSmemT<PTS>);
-    dim3 grid((a.N + PTS - 1) / PTS, a.B);
-    return CHORE_LAUNCH(h, s, (query_bwd_f32_kernel<T, TRAIN, NCB, false, 4, X3>), grid, dim3(256), smem, a);
+// the one launch of a backward kernel: grid, threads and LDS from the instantiation's constants (the kernel's own PTS)
+template <typename T, bool TRAIN, int NCB, bool STAGED, int NW, bool X3, bool SURF = false, bool ONE = false>
+static int launch_k(chore_handle* h, const QueryArgs& a, hipStream_t s) {
+    constexpr int PTS = 32 * NCB * (NW / 4);
+    return CHORE_LAUNCH(h, s, (query_bwd_f32_kernel<T, TRAIN, NCB, STAGED, NW, X3, SURF, ONE>), dim3((a.N + PTS - 1) / PTS, a.B),
+                        dim3(NW * 64), sizeof(QueryBwdSmemT<PTS>), a);
 }
 
-bool query_small_tiles(int B, int N);   // query_fwd.hip: 32-point tiles when 64-point tiles would not fill the CUs
-
-// fp16 x 3 backward, a few rounds of workgroups: a round of 64-point tiles takes 82 us, one of 32-point tiles 46 us (measured,
-// one workgroup per CU either way), so e.g. 20 000 points (313 tiles = 2 rounds, the second a fifth full) finish sooner as
-// 625 small tiles (3 rounds): 165 -> 137 us; from ~10 rounds on the 64-point tiles win on every count
-static bool x3_bwd_prefers_small(int B, int N) {
-    const long long t64 = (long long)B * ((N + 63) / 64), t32 = (long long)B * ((N + 31) / 32);
-    const long long r64 = (t64 + 255) / 256, r32 = (t32 + 255) / 256;
-    return r32 * 455 < r64 * 825;
-}
-
-static bool query_one_head() { static const bool off = getenv("CHORE_QUERY_NO_ONE_HEAD") != nullptr; return !off; }   // A/B switch
-
-template <typename T, int NCB, bool SURF = true, bool ONE = false>
-static int launch_query_surf_n(chore_handle* h, const QueryArgs& a, hipStream_t s) {
-    constexpr int PTS = 32 * NCB;
-    const size_t smem = sizeof(QueryBwdSmemT<PTS>);
-    dim3 grid((a.N + PTS - 1) / PTS, a.B);
-    return CHORE_LAUNCH(h, s, (query_bwd_f32_kernel<T, false, NCB, false, 4, true, SURF, ONE>), grid, dim3(256), smem, a);
-}
-template <typename T>
-static int launch_query_surf_t(chore_handle* h, const QueryArgs& a, hipStream_t s) {
-    // 64-point tiles with the chain on two waves wherever 64-point tiles fill the CUs (the 32-point rule of the backward was
-    // measured on the one-wave chain); 32-point tiles for the small queries
-    if (query_one_head() && !query_small_tiles(a.B, a.N)) return launch_query_surf_n<T, 2, true, true>(h, a, s);
-    return (query_small_tiles(a.B, a.N) || x3_bwd_prefers_small(a.B, a.N)) ? launch_query_surf_n<T, 1>(h, a, s)
-                                                                              : launch_query_surf_n<T, 2>(h, a, s);     // as the backward
-}
-int launch_query_surface_step(chore_handle* h, int dtype, const QueryArgs& a, hipStream_t s) {      // dtype: the maps' type
-    if (dtype == CHORE_F16) return launch_query_surf_t<qh16_t>(h, a, s);
-    return dtype == CHORE_F32 ? launch_query_surf_t<float>(h, a, s) : launch_query_surf_t<unsigned short>(h, a, s);
-}
-
-// the eight-wave variants (64-point tile, two waves per head)
-template <typename T, bool TRAIN, bool STAGED, bool X3 = false>
-static int launch_query_bwd_w8(chore_handle* h, const QueryArgs& a, hipStream_t s) {
-    const size_t smem = sizeof(QueryBwdSmemT<64>);
-    dim3 grid((a.N + 63) / 64, a.B);
-    return CHORE_LAUNCH(h, s, (query_bwd_f32_kernel<T, TRAIN, 1, STAGED, 8, X3>), grid, dim3(512), smem, a);
-}
-
-static bool query_w4() { static const bool v = getenv("CHORE_QUERY_W4") != nullptr; return v; }   // A/B switch
-
-template <typename T, bool TRAIN, bool X3 = false>
-static int launch_query_bwd_t(chore_handle* h, const QueryArgs& a, hipStream_t s) {
-    if constexpr (!TRAIN && X3) {
-        // one upstream gradient (the generator's steps, most fit phases): the head's chain on two waves of a 64-point tile
-        int live = 0, which = 0;
-        for (int i = 0; i < HEAD_NUM; ++i)
-            if (a.g[i]) { ++live; which = i; }
-        if (live == 1 && query_one_head() && !query_small_tiles(a.B, a.N)) {
-            QueryArgs b = a;
-            b.one_head = which;
-            return launch_query_surf_n<T, 2, false, true>(h, b, s);
+// plan -> instantiation, for one type of the maps and one arithmetic of the heads
+template <typename T, bool X3>
+static int launch_query_bwd_t(chore_handle* h, const QueryPlan& p, const QueryArgs& a, hipStream_t s) {
+    constexpr bool H16 = std::is_same<T, qh16_t>::value;      // fp16 maps: an inference mode of the fp16 x 3 heads
+    const bool w8 = p.waves == 8 && p.ncb == 1, w4 = p.waves == 4 && (p.ncb == 1 || p.ncb == 2);
+    if (p.train) {
+        if constexpr (X3 && !H16) {
+            if (p.staged && w8) return launch_k<T, true, 1, true, 8, true>(h, a, s);
+        } else if constexpr (!X3) {
+            if (w4 && p.ncb == 2) return p.staged ? launch_k<T, true, 2, true, 4, false>(h, a, s) : launch_k<T, true, 2, false, 4, false>(h, a, s);
         }
+    } else if (w4 && (p.one || p.surf)) {
+        if constexpr (X3) {
+            if (p.one && p.ncb == 2) return p.surf ? launch_k<T, false, 2, false, 4, true, true, true>(h, a, s) : launch_k<T, false, 2, false, 4, true, false, true>(h, a, s);
+            if (!p.one) return p.ncb == 1 ? launch_k<T, false, 1, false, 4, true, true>(h, a, s) : launch_k<T, false, 2, false, 4, true, true>(h, a, s);
+        }
+    } else if (w4) {
+        return p.ncb == 1 ? launch_k<T, false, 1, false, 4, X3>(h, a, s) : launch_k<T, false, 2, false, 4, X3>(h, a, s);
+    } else if (w8) {
+        if constexpr (!X3) return launch_k<T, false, 1, false, 8, false>(h, a, s);
     }
-    if constexpr (!TRAIN) {
-        if (query_small_tiles(a.B, a.N) || (X3 && x3_bwd_prefers_small(a.B, a.N)))
-            return launch_query_bwd_n<T, false, 1, X3>(h, a, s);
-    }
-    // the training variants are bound by their staging stores: measured slower with eight waves (39.4 vs 38.6 ms per step)
-    // fp16 x 3: four waves with two column blocks each, like the forward (the eight-wave kernel fetches every weight
-    // fragment twice and is bound by the L1: 0.65 against 0.58 ms at 4 x 20 000 points)
-    if constexpr (!TRAIN && !X3) {
-        if (!query_w4()) return launch_query_bwd_w8<T, false, false, X3>(h, a, s);
-    }
-    // (an eight-wave fp16 x 3 RECOMPUTE kernel existed behind a switch through round 3: slower, and in round 2 it produced a
-    // non-finite gradient about once in six runs of the graph-replayed fit that was never reproduced afterwards; removed in round 4)
-    return launch_query_bwd_n<T, TRAIN, 2, X3>(h, a, s);
+    CHORE_FAIL(h, CHORE_EINVAL, "launch_query_bwd: no kernel for this plan (NCB %d, %d waves, train %d, staged %d)", p.ncb, p.waves, (int)p.train, (int)p.staged);
 }
 
-template <typename T>
-static int launch_query_bwd_staged_x3(chore_handle* h, const QueryArgs& a, hipStream_t s) {
-    return launch_query_bwd_w8<T, true, true, true>(h, a, s);     // no recompute: the eight-wave kernel fits its registers
-}
-
-template <typename T>
-static int launch_query_bwd_staged_t(chore_handle* h, const QueryArgs& a, hipStream_t s) {
-    const size_t smem = sizeof(QueryBwdSmemT<64>);
-    dim3 grid((a.N + 63) / 64, a.B);
-    return CHORE_LAUNCH(h, s, (query_bwd_f32_kernel<T, true, 2, true>), grid, dim3(256), smem, a);
-}
-
-int launch_query_bwd_f32(chore_handle* h, const QueryArgs& a, hipStream_t s) {
-    return launch_query_bwd_t<float, false>(h, a, s);
-}
-int launch_query_bwd_f32_bf16maps(chore_handle* h, const QueryArgs& a, hipStream_t s) {
-    return launch_query_bwd_t<unsigned short, false>(h, a, s);
-}
-int launch_query_bwd_x3(chore_handle* h, int dtype, const QueryArgs& a, hipStream_t s) {      // dtype: the maps' type
-    if (dtype == CHORE_F16) return launch_query_bwd_t<qh16_t, false, true>(h, a, s);
-    return dtype == CHORE_F32 ? launch_query_bwd_t<float, false, true>(h, a, s) : launch_query_bwd_t<unsigned short, false, true>(h, a, s);
-}
-
-int launch_query_bwd_train(chore_handle* h, int dtype, const QueryArgs& a, hipStream_t s, int staged, int x3) {
-    if (staged && x3) return dtype == CHORE_F32 ? launch_query_bwd_staged_x3<float>(h, a, s) : launch_query_bwd_staged_x3<unsigned short>(h, a, s);
-    if (staged) return dtype == CHORE_F32 ? launch_query_bwd_staged_t<float>(h, a, s) : launch_query_bwd_staged_t<unsigned short>(h, a, s);
-    return dtype == CHORE_F32 ? launch_query_bwd_t<float, true>(h, a, s) : launch_query_bwd_t<unsigned short, true>(h, a, s);
+int launch_query_bwd(chore_handle* h, const QueryPlan& p, const QueryArgs& a0, hipStream_t s) {
+    QueryArgs a = a0;
+    a.one_head = p.one_head;
+    if (p.dtype == CHORE_F16 && !p.x3) CHORE_FAIL(h, CHORE_EINVAL, "launch_query_bwd: fp16 maps only with the fp16 x 3 heads");
+    if (p.dtype == CHORE_F16) return launch_query_bwd_t<qh16_t, true>(h, p, a, s);
+    if (p.x3) return p.dtype == CHORE_F32 ? launch_query_bwd_t<float, true>(h, p, a, s) : launch_query_bwd_t<unsigned short, true>(h, p, a, s);
+    return p.dtype == CHORE_F32 ? launch_query_bwd_t<float, false>(h, p, a, s) : launch_query_bwd_t<unsigned short, false>(h, p, a, s);
 }

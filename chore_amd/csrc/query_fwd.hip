@@ -12,7 +12,6 @@
 // heads_pack.  Phase 4: masked (df[~in_img] = 5.0, model/chore.py:147-150) coalesced stores in the
 // (B,C,N) layout the reference API returns.
 #include "heads_x3.h"
-#include <cstdlib>
 
 template <int PTS>
 struct QueryFwdSmemT {
@@ -479,14 +478,6 @@ __global__ __launch_bounds__(512, 1) void query_fwd_x3_split_kernel(QueryArgs a)
     QSTAMP(5);
 }
 
-template <typename T, int NCB>
-static int launch_query_fwd_split(chore_handle* h, const QueryArgs& a, hipStream_t s) {
-    constexpr int PTS = 32 * NCB;
-    const size_t smem = sizeof(QuerySplitSmemT<PTS>);
-    dim3 grid((a.N + PTS - 1) / PTS, a.B);
-    return CHORE_LAUNCH(h, s, (query_fwd_x3_split_kernel<T, NCB>), grid, dim3(512), smem, a);
-}
-
 // ------------------------------------------------------------------------------------------------
 // pixel-aligned feature sample only (projection + 2x index + z_feat, no heads): the 323-vector per
 // point, point-major.  Same phase 1/2 code as the fused kernel, so it doubles as its probe.
@@ -717,71 +708,40 @@ int launch_heads_pack_f32(chore_handle* h, const HeadsRaw& raw, float* arena, hi
 
 size_t heads_arena_bytes() { return QX_ARENA_BYTES; }
 
-template <typename T, int NCB, bool X3 = false>
-static int launch_query_fwd_n(chore_handle* h, const QueryArgs& a, hipStream_t s) {
-    constexpr int PTS = 32 * NCB;
-    const size_t smem = sizeof(QueryFwdSmemT<PTS>);
-    dim3 grid((a.N + PTS - 1) / PTS, a.B);
-    return CHORE_LAUNCH(h, s, (query_fwd_f32_kernel<T, NCB, false, X3>), grid, dim3(256), smem, a);
+// the one launch of a forward kernel: PTS points per workgroup of NW waves, the LDS of the instantiation's struct (+ extra)
+template <int PTS, int NW, typename Smem, typename... P>
+static int launch_tiles(chore_handle* h, hipStream_t s, void (*kernel)(P...), const QueryArgs& a, size_t extra = 0) {
+    return CHORE_LAUNCH(h, s, kernel, dim3((a.N + PTS - 1) / PTS, a.B), dim3(NW * 64), sizeof(Smem) + extra, a);
 }
 
-// 64-point tiles unless they would leave CUs without a workgroup
-bool query_small_tiles(int B, int N) { return (size_t)B * ((N + QT_PTS - 1) / QT_PTS) <= 256; }
-
-template <typename T>
-static int launch_query_fwd_w8(chore_handle* h, const QueryArgs& a, hipStream_t s) {
-    const size_t smem = sizeof(QueryFwdSmemT<64>);
-    dim3 grid((a.N + 63) / 64, a.B);
-    return CHORE_LAUNCH(h, s, (query_fwd_f32_w8_kernel<T, false, false>), grid, dim3(512), smem, a);
-}
-
-// CHORE_QUERY_W4=1 (A/B switch): the four-wave kernel where the eight-wave one is the default -- the fp32-MFMA heads' large
-// inference queries (here and in query_bwd.hip) and the training forward
-static bool query_w4() { static const bool v = getenv("CHORE_QUERY_W4") != nullptr; return v; }
-
-template <typename T, bool X3 = false>
-static int launch_query_fwd_t(chore_handle* h, const QueryArgs& a, hipStream_t s) {
+// plan -> instantiation, for one type of the maps and one arithmetic of the heads
+template <typename T, bool X3>
+static int launch_query_fwd_t(chore_handle* h, const QueryPlan& p, const QueryArgs& a, hipStream_t s) {
+    constexpr bool H16 = std::is_same<T, qh16_t>::value;      // fp16 maps: an inference mode of the fp16 x 3 heads
+    const bool w8 = p.family == QUERY_K_FWD8, w4 = p.family == QUERY_K_FWD4;
     if constexpr (X3) {
-        static const bool nosplit = getenv("CHORE_QUERY_X3_NOSPLIT") != nullptr;      // A/B switch: the one-wave-per-head kernels
-        if (!nosplit) return query_small_tiles(a.B, a.N) ? launch_query_fwd_split<T, 1>(h, a, s) : launch_query_fwd_split<T, 2>(h, a, s);
+        if (p.family == QUERY_K_SPLIT && !p.train)
+            return p.ncb == 1 ? launch_tiles<32, 8, QuerySplitSmemT<32>>(h, s, query_fwd_x3_split_kernel<T, 1>, a)
+                              : launch_tiles<64, 8, QuerySplitSmemT<64>>(h, s, query_fwd_x3_split_kernel<T, 2>, a);
     }
-    if (query_small_tiles(a.B, a.N)) return launch_query_fwd_n<T, 1, X3>(h, a, s);
-    // (a single output asked for, CHORE.query_df: 32-point tiles do not pay -- a workgroup is placed with the registers of all
-    // four waves, so the CU holds one whatever the three leaving waves free: 363 against 335 us at 8 x 20 000 points)
-    // fp16 x 3: a k-step of MFMAs is 2.7 x shorter than the fp32 one for the same weight bytes, and the eight-wave kernel
-    // (both waves of a head fetch the head's fragments) is bound by the L1's 64 B / clk: 0.227 ms against 0.203 ms for
-    // four waves with two column blocks each (4 x 20 000 points; the eight-wave fp16 x 3 inference kernel was removed in round 8)
-    if constexpr (X3) return launch_query_fwd_n<T, 2, true>(h, a, s);
-    else return query_w4() ? launch_query_fwd_n<T, 2>(h, a, s) : launch_query_fwd_w8<T>(h, a, s);
+    if constexpr (!H16) {
+        if (p.train && w8)      // + the waves' store-transpose tiles
+            return launch_tiles<64, 8, QueryFwdSmemT<64>>(h, s, query_fwd_f32_w8_kernel<T, true, X3>, a, 8 * 32 * ST_LD * sizeof(float));
+        if (p.train && w4 && p.ncb == 2) return launch_tiles<64, 4, QueryFwdSmemT<64>>(h, s, query_fwd_f32_kernel<T, 2, true, X3>, a);
+    }
+    if constexpr (!X3) {
+        if (!p.train && w8) return launch_tiles<64, 8, QueryFwdSmemT<64>>(h, s, query_fwd_f32_w8_kernel<T, false, false>, a);
+    }
+    if (!p.train && w4)
+        return p.ncb == 1 ? launch_tiles<32, 4, QueryFwdSmemT<32>>(h, s, query_fwd_f32_kernel<T, 1, false, X3>, a)
+                          : launch_tiles<64, 4, QueryFwdSmemT<64>>(h, s, query_fwd_f32_kernel<T, 2, false, X3>, a);
+    CHORE_FAIL(h, CHORE_EINVAL, "launch_query_fwd: no kernel for this plan (family %d, NCB %d, train %d)", p.family, p.ncb, (int)p.train);
 }
 
-template <typename T, bool X3 = false>
-static int launch_query_fwd_train_w8(chore_handle* h, const QueryArgs& a, hipStream_t s) {
-    const size_t smem = sizeof(QueryFwdSmemT<64>) + 8 * 32 * ST_LD * sizeof(float);     // + the waves' store-transpose tiles
-    dim3 grid((a.N + 63) / 64, a.B);
-    return CHORE_LAUNCH(h, s, (query_fwd_f32_w8_kernel<T, true, X3>), grid, dim3(512), smem, a);
+int launch_query_fwd(chore_handle* h, const QueryPlan& p, const QueryArgs& a, hipStream_t s) {
+    if (p.dtype == CHORE_F16 && !p.x3) CHORE_FAIL(h, CHORE_EINVAL, "launch_query_fwd: fp16 maps only with the fp16 x 3 heads");
+    if (p.dtype == CHORE_F16) return launch_query_fwd_t<qh16_t, true>(h, p, a, s);
+    if (p.x3) return p.dtype == CHORE_F32 ? launch_query_fwd_t<float, true>(h, p, a, s) : launch_query_fwd_t<unsigned short, true>(h, p, a, s);
+    return p.dtype == CHORE_F32 ? launch_query_fwd_t<float, false>(h, p, a, s) : launch_query_fwd_t<unsigned short, false>(h, p, a, s);
 }
 
-template <typename T, bool X3 = false>
-static int launch_query_fwd_train_t(chore_handle* h, const QueryArgs& a, hipStream_t s) {
-    if (!query_w4()) return launch_query_fwd_train_w8<T, X3>(h, a, s);
-    const size_t smem = sizeof(QueryFwdSmemT<64>);
-    dim3 grid((a.N + 63) / 64, a.B);
-    return CHORE_LAUNCH(h, s, (query_fwd_f32_kernel<T, 2, true, X3>), grid, dim3(256), smem, a);
-}
-// x3: the heads on the fp16 matrix cores with split operands (either map type)
-int launch_query_fwd_train(chore_handle* h, int dtype, const QueryArgs& a, hipStream_t s, int x3) {
-    if (x3) return dtype == CHORE_F32 ? launch_query_fwd_train_t<float, true>(h, a, s) : launch_query_fwd_train_t<unsigned short, true>(h, a, s);
-    return dtype == CHORE_F32 ? launch_query_fwd_train_t<float>(h, a, s) : launch_query_fwd_train_t<unsigned short>(h, a, s);
-}
-
-int launch_query_fwd_f32(chore_handle* h, const QueryArgs& a, hipStream_t s) {
-    return launch_query_fwd_t<float>(h, a, s);
-}
-int launch_query_fwd_f32_bf16maps(chore_handle* h, const QueryArgs& a, hipStream_t s) {
-    return launch_query_fwd_t<unsigned short>(h, a, s);
-}
-int launch_query_fwd_x3(chore_handle* h, int dtype, const QueryArgs& a, hipStream_t s) {      // dtype: the maps' type
-    if (dtype == CHORE_F16) return launch_query_fwd_t<qh16_t, true>(h, a, s);
-    return dtype == CHORE_F32 ? launch_query_fwd_t<float, true>(h, a, s) : launch_query_fwd_t<unsigned short, true>(h, a, s);
-}

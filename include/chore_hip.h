@@ -899,6 +899,23 @@ int chore_debug_last_conv(chore_handle* h, int* out, int n);
  *   out[7] weight-gradient launches on the handle so far
  * Host stores only: no kernel and no result changes. */
 int chore_debug_last_wgrad(chore_handle* h, int* out, int n);
+/* which kernel a query call runs (csrc/query_plan.h; no handle, no device): what the entry point decides for these arguments.
+ *   op         0 chore_query_fwd[_ws], 1 chore_query_fwd_train, 2 chore_query_bwd_points, 3 chore_gen_surface_step_fused,
+ *              4 chore_query_bwd_train
+ *   dtype      as the entry point takes it, CHORE_HEADS_X3 included     B, N, FH, FW  as there (the other map never matters)
+ *   live_mask  op 2: bit 0 g_df, bit 1 g_parts, bit 2 g_pca, bit 3 g_centers is not NULL
+ *   flags      bit 0: a workspace is passed (op 0), bit 1: have_forward (op 4)
+ *   switches   bit 0 CHORE_QUERY_W4, bit 1 CHORE_QUERY_X3_NOSPLIT, bit 2 CHORE_QUERY_NO_ONE_HEAD; -1: this process's
+ *              environment, as the entry points read it -- once, before their first call
+ * Writes min(n, 9) ints and returns that count, or CHORE_EINVAL for a bad argument and for what the entry point refuses (fp16
+ * maps in training, fp16 x 3 training backward without the staged forward, a surface step without the fp16 x 3 heads):
+ *   out[0] kernel: 0 query_fwd_x3_split_kernel, 1 query_fwd_f32_kernel, 2 query_fwd_f32_w8_kernel, 3 query_bwd_f32_kernel
+ *   out[1] the template's NCB (1 in the eight-wave kernels)   out[2] waves of a workgroup (the template's NW: 4 or 8)
+ *   out[3] template flags: 1 TRAIN, 2 STAGED, 4 X3 (heads on the fp16 matrix cores), 8 SURF, 16 ONE
+ *   out[4] ONE without SURF: the head that has the gradient (0 df, 1 parts, 2 pca, 3 centers)
+ *   out[5] points of a tile   out[6] threads of a workgroup   out[7] 1: the sort runs first (query_bin_kernel, query_perm_kernel)
+ *   out[8] the kernel's T: the maps' type (CHORE_F32 float, CHORE_BF16 unsigned short, CHORE_F16 qh16_t) */
+int chore_query_plan(int op, int dtype, int B, int N, int FH, int FW, int live_mask, int flags, int switches, int* out, int n);
 
 #ifdef __cplusplus
 }
