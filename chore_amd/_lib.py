@@ -116,6 +116,7 @@ SIGNATURES = {
     "chore_debug_last_conv": (c_int, [c_void_p, POINTER(c_int), c_int]),
     "chore_debug_last_wgrad": (c_int, [c_void_p, POINTER(c_int), c_int]),
     "chore_query_plan": (c_int, [c_int] * 9 + [POINTER(c_int), c_int]),
+    "chore_conv_plan": (c_int, [c_int] * 9 + [POINTER(c_int), c_int]),
     "chore_fit_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_float, c_float,
                                     c_float, c_float, c_void_p, c_void_p]),
     "chore_fit_adam_step_acc": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,

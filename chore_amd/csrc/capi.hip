@@ -212,6 +212,20 @@ int chore_query_plan(int op, int dtype, int B, int N, int FH, int FW, int live_m
     return k;
 }
 
+int chore_conv_plan(int dtype, int taps, int B, int H, int W, int Cin, int Cout, int traits_bits, int fill, int* out, int n) {
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || !out || n <= 0) return CHORE_EINVAL;
+    ConvTraits t;
+    t.gn = traits_bits & CONV_TRAIT_GN; t.scaled = traits_bits & CONV_TRAIT_SCALED; t.res = traits_bits & CONV_TRAIT_RES;
+    t.res2 = traits_bits & CONV_TRAIT_RES2; t.pool = traits_bits & CONV_TRAIT_POOL; t.out = traits_bits & CONV_TRAIT_OUT;
+    t.fill = fill;
+    const ConvLaunchPlan p = conv_launch_plan(dtype, taps, B, H, W, Cin, Cout, t, conv_switches());
+    if (p.refuse[0]) return CHORE_EINVAL;
+    const int v[7] = {p.family, p.rows, p.nt, p.tps, p.nslot, p.flags, conv_profile_class(p, taps, Cin)};
+    const int k = n < 7 ? n : 7;
+    for (int i = 0; i < k; ++i) out[i] = v[i];
+    return k;
+}
+
 size_t chore_query_fwd_workspace_bytes(int B, int N) {
     if (B <= 0 || N <= 0) return 0;
     return (size_t)B * query_sort_ints(N) * sizeof(int);

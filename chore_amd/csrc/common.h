@@ -9,6 +9,7 @@
 #include <unordered_map>
 #include "../../include/chore_hip.h"
 #include "query_plan.h"
+#include "conv_plan.h"
 
 struct chore_handle {
     int device = 0;
@@ -32,12 +33,10 @@ struct chore_handle {
     // pixel tiles, flags, and the number of weight-gradient launches so far
     int last_wgrad[8] = {};
 };
-// kernel families and flag bits of chore_handle::last_conv (include/chore_hip.h, chore_debug_last_conv)
-enum { CONV_FAM_LDS = 1, CONV_FAM_SMALL = 2, CONV_FAM_PC = 3, CONV_FAM_MW = 4, CONV_FAM_RW = 5 };
-enum { CONV_FLAG_SCALED = 1, CONV_FLAG_GN = 2, CONV_FLAG_SMALL_GRID = 4, CONV_FLAG_RES = 8, CONV_FLAG_POOL = 16 };
-inline void chore_note_conv(chore_handle* h, int family, int rows, int nt, int tps, int nslot, int flags, int cin) {
+// launch_conv notes the plan it launches (conv_plan.h has the families and flag bits)
+inline void chore_note_conv(chore_handle* h, const ConvLaunchPlan& p, int cin) {
     int* r = h->last_conv;
-    r[0] = family; r[1] = rows; r[2] = nt; r[3] = tps; r[4] = nslot; r[5] = flags; r[6] = cin; ++r[7];
+    r[0] = p.family; r[1] = p.rows; r[2] = p.nt; r[3] = p.tps; r[4] = p.nslot; r[5] = p.flags; r[6] = cin; ++r[7];
 }
 // kernels and flag bits of chore_handle::last_wgrad (include/chore_hip.h, chore_debug_last_wgrad)
 enum { WGRAD_K_W32 = 1, WGRAD_K_W64 = 2, WGRAD_K_W64X3 = 3, WGRAD_K_W64X3PC = 4, WGRAD_K_W128X3PC = 5 };

@@ -494,7 +494,7 @@ int launch_nt(chore_handle* h, int nt, bool small_grid, const ConvArgs& a, hipSt
             if (small_grid && nt == 64) return launch_t<T, 9, 64, 9>(h, a, s);
             if (small_grid && nt == 32) return launch_t<T, 9, 32, 9>(h, a, s);
         }
-        if constexpr (sizeof(T) == 2) {   // the 4x2 register tile is bf16-only (choose_nt never picks it for fp32)
+        if constexpr (sizeof(T) == 2) {   // the 4x2 register tile is bf16-only (conv_lds_nt never picks it for fp32)
             if (nt == 128) return launch_t<T, 9, 128, 3>(h, a, s);
         }
         if (nt == 64) return launch_t<T, 9, 64, 3>(h, a, s);
@@ -508,115 +508,38 @@ int launch_nt(chore_handle* h, int nt, bool small_grid, const ConvArgs& a, hipSt
     }
 }
 
-int tiles_of(int H, int W) { return ((W + TW - 1) / TW) * ((H + TH - 1) / TH); }
+static_assert(TH == CONV_LDS_TH && TW == CONV_LDS_TW && PD_SMALL == CONV_LDS_PD_SMALL, "conv_plan.h counts this kernel's workgroups and chunks");
 
-// N-tile choice: the largest channel tile that still gives every CU about two workgroups
-int choose_nt(int dtype, int B, int H, int W, int Cout) {
-    static const int nts[3] = {128, 64, 32};
-    int best = 32;
-    long best_wgs = -1;
-    for (int i = 0; i < 3; ++i) {
-        const int nt = nts[i];
-        if (Cout % nt) continue;
-        if (nt == 128 && dtype != CHORE_BF16) continue;  // the 4x2 register tile fits 256 VGPRs with bf16 operands only
-        const long wgs = (long)B * tiles_of(H, W) * (Cout / nt);
-        if (wgs >= 448) return nt;
-        if (wgs > best_wgs) { best_wgs = wgs; best = nt; }
-    }
-    return best;
+template <typename T>
+int launch_lds(chore_handle* h, int taps, const ConvLaunchPlan& p, const ConvArgs& a, hipStream_t s) {
+    return taps == 9 ? launch_nt<T, 9>(h, p.nt, p.small_grid, a, s) : launch_nt<T, 1>(h, p.nt, p.small_grid, a, s);
 }
 
-}  // namespace
-
-// small grid: fewer workgroups than 1.5 per CU -> whole-chunk K-steps with deep register prefetch (needs the chunk
-// count to be a multiple of the prefetch distance)
-static bool is_small_grid(int dtype, int B, int H, int W, int Cin, int Cout, int nt) {
-    const int nch = Cin / (dtype == CHORE_F32 ? 16 : 32);
-    if (dtype == CHORE_F16X3) return false;
-    return nt <= 64 && nch % PD_SMALL == 0 && (long)B * tiles_of(H, W) * (Cout / nt) < 384;
-}
-
-// CHORE_CONV_LDS=1: every layer on conv_lds_kernel (A/B measurements against the specialised-wave kernel)
-bool conv_use_pc() {
-    static const bool off = getenv("CHORE_CONV_LDS") != nullptr;
-    return !off;
-}
-
-ConvPlan conv_plan(int dtype, int taps, int B, int H, int W, int Cin, int Cout) {
-    if (conv_small_eligible(dtype, taps, H, W, Cin, Cout)) return ConvPlan{32, 1, H * (W / 32), 0, Cin};
-    const int nt = choose_nt(dtype, B, H, W, Cout);
-    const int tps = taps == 1 ? 1 : (is_small_grid(dtype, B, H, W, Cin, Cout, nt) ? 9 : 3);
-    return ConvPlan{nt, TH, tiles_of(H, W), tps, 0};
-}
-
-bool conv_pool_covers(int dtype, int taps, int Cin, int Cout, int H, int W) {
-    return conv_use_pc() && conv_mw_pool_covers(dtype, taps, Cin, Cout, H, W);
-}
-
-int launch_conv(chore_handle* h, int dtype, int taps, const ConvArgs& a_in, hipStream_t s) {
-    const int cc = dtype == CHORE_F32 ? 16 : 32;
-    if (dtype != CHORE_F32 && dtype != CHORE_BF16 && dtype != CHORE_F16X3 && dtype != CHORE_F16) CHORE_FAIL(h, CHORE_EINVAL, "conv: bad dtype");
-    if (a_in.in.C % cc || a_in.in.C > 256) CHORE_FAIL(h, CHORE_EINVAL, "conv: unsupported Cin=%d", a_in.in.C);
-    if (a_in.Cout % 32) CHORE_FAIL(h, CHORE_EINVAL, "conv: unsupported Cout=%d", a_in.Cout);
-    if (a_in.B > 65535) CHORE_FAIL(h, CHORE_EINVAL, "conv: B too large");
-    if (taps != 1 && taps != 9) CHORE_FAIL(h, CHORE_EINVAL, "conv: taps must be 1 or 9");
-    for (int c : {a_in.st_raw ? a_in.st_raw_C : 32, a_in.st_out ? a_in.st_out_C : 32, a_in.in_st ? a_in.in.C : 32}) {
-        const int gs = c / GN_GROUPS;
-        if (c % GN_GROUPS || gs > 8 || (gs & (gs - 1)))
-            CHORE_FAIL(h, CHORE_EINVAL, "conv: GroupNorm over %d channels unsupported (group size must be 1, 2, 4 or 8)", c);
-    }
-    if (a_in.pool.p) {   // a pooled output rides in conv_mw_kernel's epilogue only: the caller asked conv_pool_covers() first
-        const PcPlan mp = conv_mw_plan(dtype, taps, a_in.B, a_in.H, a_in.W, a_in.in.C, a_in.Cout, a_in.fill);
-        if (a_in.st_pool && (a_in.st_pool_C % GN_GROUPS || a_in.st_pool_C / GN_GROUPS > 8 || ((a_in.st_pool_C / GN_GROUPS) & (a_in.st_pool_C / GN_GROUPS - 1))))
-            CHORE_FAIL(h, CHORE_EINVAL, "conv: GroupNorm over %d channels unsupported (group size must be 1, 2, 4 or 8)", a_in.st_pool_C);
-        if (!conv_pool_covers(dtype, taps, a_in.in.C, a_in.Cout, a_in.H, a_in.W) || !mp.th || !conv_mw_covers(dtype, taps, mp, a_in))
-            CHORE_FAIL(h, CHORE_EINVAL, "conv: this launch cannot carry a pooled output (taps=%d Cin=%d Cout=%d %dx%d)", taps, a_in.in.C, a_in.Cout, a_in.H, a_in.W);
-        return launch_conv_mw(h, dtype, taps, mp, a_in, s);
-    }
-    if (!a_in.out.p) CHORE_FAIL(h, CHORE_EINVAL, "conv: no output");
-    if (conv_mw_on(dtype, taps) && conv_mw_fill(a_in.fill) < 256 && !a_in.res2.p) {      // the small maps on dense conv_mw tiles (conv_mw_plan)
-        const PcPlan mp = conv_mw_plan(dtype, taps, a_in.B, a_in.H, a_in.W, a_in.in.C, a_in.Cout, a_in.fill);
-        if (mp.th && conv_mw_covers(dtype, taps, mp, a_in)) return launch_conv_mw(h, dtype, taps, mp, a_in, s);
-    }
-    if (conv_small_eligible(dtype, taps, a_in.H, a_in.W, a_in.in.C, a_in.Cout)) return launch_conv_small(h, dtype, a_in, s);
-    // 1x1 (every 16-bit-operand mode): weights resident in registers, persistent workgroups (conv_rw.hip; fp16 x 3 256 -> 256 at 128^2: 64 -> 39 us)
-    if (conv_rw_eligible(dtype, taps, a_in) && conv_use_pc()) return launch_conv_rw(h, dtype, a_in, s);
-    if (dtype == CHORE_F16) {   // fp16 tensors: the specialised-wave kernel is the only implementation
-        const PcPlan pp = conv_pc_plan(dtype, taps, a_in.B, a_in.H, a_in.W, a_in.in.C, a_in.Cout);
-        if (!pp.th || a_in.res2.p) CHORE_FAIL(h, CHORE_EINVAL, "conv: layer not covered in the fp16 mode (Cin=%d Cout=%d)", a_in.in.C, a_in.Cout);
-        return launch_conv_pc(h, dtype, taps, pp, a_in, s);
-    }
-    // specialised-wave kernel (conv_pc.hip): fp16 x 3; since round 5 also bf16, where it measured faster layer by layer
-    // (profiles/r05_conv_layer_ab.txt: 3x3 layers of <= 128 input channels on maps up to 128^2 -- 64^2 128->64 15.4 against 20.2 us,
-    // 64->64 13.2 against 15.7; the 1x1 layers, the 256-channel inputs and the 256^2 maps stay on conv_lds_kernel, which wins there:
-    // with one MFMA per product the bf16 K loop is short and the producer / consumer hand-over costs more than it hides).
-    // CHORE_CONV_LDS_BF16=1: conv_lds_kernel everywhere (rounds 1 - 4); CHORE_CONV_PC_BF16=1: conv_pc_kernel wherever it has a tiling
-    static const bool bf16_lds = getenv("CHORE_CONV_LDS_BF16") != nullptr, bf16_pc_all = getenv("CHORE_CONV_PC_BF16") != nullptr;
-    const bool bf16_pc = dtype == CHORE_BF16 && !bf16_lds &&
-                         (bf16_pc_all || (taps == 9 && a_in.in.C <= 128 && (long)a_in.H * a_in.W <= 128 * 128));
-    if ((dtype == CHORE_F16X3 || bf16_pc) && !a_in.res2.p && conv_use_pc()) {
-        if (conv_mw_on(dtype, taps)) {
-            const PcPlan mp = conv_mw_plan(dtype, taps, a_in.B, a_in.H, a_in.W, a_in.in.C, a_in.Cout, a_in.fill);
-            if (mp.th && conv_mw_covers(dtype, taps, mp, a_in)) return launch_conv_mw(h, dtype, taps, mp, a_in, s);
-        }
-        const PcPlan pp = conv_pc_plan(dtype, taps, a_in.B, a_in.H, a_in.W, a_in.in.C, a_in.Cout);
-        if (pp.th) return launch_conv_pc(h, dtype, taps, pp, a_in, s);
-    }
+int launch_conv_lds(chore_handle* h, int dtype, int taps, const ConvLaunchPlan& p, const ConvArgs& a_in, hipStream_t s) {
     ConvArgs a = a_in;
 #if CHORE_CONV_ABLATE
     static const int dbg = getenv("CHORE_CONV_DBG") ? atoi(getenv("CHORE_CONV_DBG")) : 0;
     a.dbg = (a_in.dbg & (1 << 30)) ? (a_in.dbg & ~(1 << 30)) : dbg;   // bit 30: the caller's switches (scripts/probes/conv_bench.hip)
 #endif
-    const int nt = choose_nt(dtype, a.B, a.H, a.W, a.Cout);
-    const bool small_grid = is_small_grid(dtype, a.B, a.H, a.W, a.in.C, a.Cout, nt);
-    // (taps per K-step as conv_plan derives them and as launch_nt instantiates them below: 9 for the small grid, else 3; keep the three alike)
-    chore_note_conv(h, CONV_FAM_LDS, TH, nt, taps == 1 ? 1 : (small_grid ? 9 : 3), 2, conv_note_flags(a, small_grid), a.in.C);
-    if (dtype == CHORE_F32)
-        return taps == 9 ? launch_nt<float, 9>(h, nt, small_grid, a, s) : launch_nt<float, 1>(h, nt, small_grid, a, s);
-    if (dtype == CHORE_F16X3)
-        return a.in_amax ? (taps == 9 ? launch_nt<x3s_t, 9>(h, nt, false, a, s) : launch_nt<x3s_t, 1>(h, nt, false, a, s))
-                         : (taps == 9 ? launch_nt<x3_t, 9>(h, nt, false, a, s) : launch_nt<x3_t, 1>(h, nt, false, a, s));
-    return taps == 9 ? launch_nt<bf16_t, 9>(h, nt, small_grid, a, s) : launch_nt<bf16_t, 1>(h, nt, small_grid, a, s);
+    if (dtype == CHORE_F32) return launch_lds<float>(h, taps, p, a, s);
+    if (dtype == CHORE_F16X3) return a.in_amax ? launch_lds<x3s_t>(h, taps, p, a, s) : launch_lds<x3_t>(h, taps, p, a, s);
+    return launch_lds<bf16_t>(h, taps, p, a, s);
+}
+
+}  // namespace
+
+// conv_plan.h decides (kernel family, tiling, flags, refusals); this maps the plan to its family's launcher
+int launch_conv(chore_handle* h, int dtype, int taps, const ConvArgs& a, hipStream_t s) {
+    const ConvLaunchPlan p = conv_launch_plan(dtype, taps, a.B, a.H, a.W, a.in.C, a.Cout, conv_traits_of(a), conv_switches());
+    if (p.refuse[0]) CHORE_FAIL(h, CHORE_EINVAL, "%s", p.refuse);
+    chore_note_conv(h, p, a.in.C);
+    switch (p.family) {
+    case CONV_FAM_MW: return launch_conv_mw(h, dtype, taps, p, a, s);
+    case CONV_FAM_SMALL: return launch_conv_small(h, dtype, p, a, s);
+    case CONV_FAM_RW: return launch_conv_rw(h, dtype, a, s);
+    case CONV_FAM_PC: return launch_conv_pc(h, dtype, taps, p, a, s);
+    }
+    return launch_conv_lds(h, dtype, taps, p, a, s);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -737,71 +737,10 @@ int launch_mw_t(chore_handle* h, const ConvArgs& a, hipStream_t s) {
 
 }  // namespace
 
-// Which tilings of conv_pc_plan this kernel takes over: every 3x3 tiling of the fp16 x 3 mode (it measured faster or equal on every
-// layer of the encoder, profiles/r06_conv_layer_ab.txt).  CHORE_CONV_MW=0: none (A/B against conv_pc_kernel)
-int conv_mw_fill(int asked) {
-    static const int env = getenv("CHORE_CONV_MW_FILL") ? atoi(getenv("CHORE_CONV_MW_FILL")) : 0;
-    const int v = env > 0 ? env : asked;
-    return v > 0 ? v : 256;
-}
-bool conv_mw_on(int dtype, int taps) {
-    static const char* env = getenv("CHORE_CONV_MW");
-    if (env && env[0] == '0') return false;
-    return dtype == CHORE_F16X3 && taps == 9;
-}
-// The tiling for a layer: conv_pc_plan's.  CHORE_CONV_MW_TH2=1 (experiment, measured equal: 256 -> 128 at 64^2, B = 4, 41.5 - 42.4 us
-// against 40.6 - 42.4, profiles/r06_conv_layer_ab.txt): 128 output channels on maps with fewer than 256 eight-row tiles as
-// 2 x 32 pixels x 128 channels (0.4 of the 256-channel patch staged once) instead of four 32-channel workgroups per 8 x 32 pixels
-// that each stage the whole patch -- the staging is not what bounds that layer
-PcPlan conv_mw_plan(int dtype, int taps, int B, int H, int W, int Cin, int Cout, int fill_asked) {
-    PcPlan p = conv_pc_plan(dtype, taps, B, H, W, Cin, Cout);
-    static const bool th2 = getenv("CHORE_CONV_MW_TH2") != nullptr;
-    if (th2 && p.th && taps == 9 && Cout % 128 == 0 && p.nt < 128 && H % 2 == 0) {
-        const long tiles2 = (long)B * (H / 2) * ((W + 31) / 32) * (Cout / 128);
-        if (tiles2 >= 256) { p.th = 2; p.nt = 128; p.tps = 1; p.nslot = 3; }
-    }
-    // A layer too small to give every CU a full tile (the 64^2 and 32^2 maps at B = 4) takes the WIDEST tile that still yields
-    // `fill` workgroups (ConvArgs::fill; the inference encoder asks for 128 = half the CUs) instead of the narrowest that yields 256 -- fewer, denser workgroups:
-    // the same launch time on half of the CUs, the other half free for the other step in flight (two in flight 4.24 -> 3.99 ms, one
-    // at a time 5.03 -> 5.06; 64: 4.03 / 5.47; profiles/r06_conv_fill.txt).  Also takes the 32^2 maps over from conv_small_kernel.
-    // CHORE_CONV_MW_FILL=256: a tile per CU as conv_pc_plan has it.
-    const int fill = conv_mw_fill(fill_asked);
-    if (fill < 256 && taps == 9 && conv_mw_on(dtype, taps) && Cin % 32 == 0 && W % 32 == 0) {
-        const long px8 = (long)B * ((H + 7) / 8) * (W / 32);
-        if (px8 * (Cout / 32) < 256 || !p.th || (p.th == 4 && p.nt == 32) || (p.th == 8 && p.nt == 32 && px8 * (Cout / 32) < 512)) {
-            static const int cand[][4] = {{8, 128, 1, 3}, {4, 128, 1, 3}, {2, 128, 1, 3}, {8, 64, 3, 2}, {4, 64, 3, 2}, {2, 64, 1, 3},
-                                          {8, 32, 3, 2}, {4, 32, 9, 2}};
-            for (const auto& c : cand) {
-                if (Cout % c[1] || H % c[0]) continue;
-                const long wgs = (long)B * (H / c[0]) * (W / 32) * (Cout / c[1]);
-                if (wgs >= fill) { p.th = c[0]; p.nt = c[1]; p.tps = c[2]; p.nslot = c[3]; break; }
-            }
-        }
-    }
-    return p;
-}
-bool conv_mw_has(const PcPlan& p) {
-    const int key = (p.th * 1000 + p.nt) * 100 + p.tps * 10 + p.nslot;
-    return key == 812813 || key == 806432 || key == 803232 || key == 406432 || key == 403292 || key == 212813 || key == 412813 || key == 206413;
-}
-bool conv_mw_covers(int dtype, int taps, const PcPlan& p, const ConvArgs& a) {
-    if (!conv_mw_on(dtype, taps) || a.res2.p) return false;
-    if (a.in_st == nullptr && a.in_amax == nullptr) return false;      // instantiated: GroupNorm-fused forward, scaled data gradient
-    if (a.in_st != nullptr && a.in_amax != nullptr) return false;
-    return conv_mw_has(p);
-}
-
-bool conv_mw_pool_covers(int dtype, int taps, int Cin, int Cout, int H, int W) {
-    // (conv_mw_plan has a tiling for every such layer: conv_pc_plan's fall-through is 8 or 4 rows x 32 channels)
-    return conv_mw_on(dtype, taps) && Cin % 32 == 0 && Cin <= 256 && Cout % 32 == 0 && H > 0 && W > 0 && H % 2 == 0 && W % 2 == 0;
-}
-
-int launch_conv_mw(chore_handle* h, int dtype, int taps, const PcPlan& p, const ConvArgs& a, hipStream_t s) {
-    if (a.pool.p && ((a.H | a.W) & 1)) CHORE_FAIL(h, CHORE_EINVAL, "conv_mw: a pooled output needs even H and W (%d x %d)", a.H, a.W);
-    if (!a.pool.p && !a.out.p) CHORE_FAIL(h, CHORE_EINVAL, "conv_mw: no output");
-    if (a.pool.p && a.in_amax) CHORE_FAIL(h, CHORE_EINVAL, "conv_mw: no pooled output on the data-gradient kernels");
-    chore_note_conv(h, CONV_FAM_MW, p.th, p.nt, p.tps, p.nslot, conv_note_flags(a), a.in.C);
-    const int key = (p.th * 1000 + p.nt) * 100 + p.tps * 10 + p.nslot;
+// Which tilings this kernel takes over (conv_plan.h: conv_mw_tile, conv_mw_covers): every 3x3 tiling of the fp16 x 3 mode (it measured
+// faster or equal on every layer of the encoder, profiles/r06_conv_layer_ab.txt).  The plan's tiling -> its instantiation
+int launch_conv_mw(chore_handle* h, int dtype, int taps, const ConvLaunchPlan& p, const ConvArgs& a, hipStream_t s) {
+    const int key = (p.rows * 1000 + p.nt) * 100 + p.tps * 10 + p.nslot;
 #define MW_CASE(TH, NT, TPS, NSLOT) \
     case (TH * 1000 + NT) * 100 + TPS * 10 + NSLOT:                                              \
         return a.in_amax ? launch_mw_t<x3_t, 9, TH, NT, TPS, NSLOT, false, true>(h, a, s)         \
@@ -818,5 +757,5 @@ int launch_conv_mw(chore_handle* h, int dtype, int taps, const PcPlan& p, const 
         MW_CASE(4, 32, 9, 2);
     }
 #undef MW_CASE
-    CHORE_FAIL(h, CHORE_EINVAL, "conv_mw: no kernel for taps=%d th=%d nt=%d tps=%d nslot=%d", taps, p.th, p.nt, p.tps, p.nslot);
+    CHORE_FAIL(h, CHORE_EINVAL, "conv_mw: no kernel for taps=%d th=%d nt=%d tps=%d nslot=%d", taps, p.rows, p.nt, p.tps, p.nslot);
 }

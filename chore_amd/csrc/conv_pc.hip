@@ -681,58 +681,9 @@ int launch_pc_t(chore_handle* h, const ConvArgs& a, hipStream_t s) {
 
 }  // namespace
 
-// tile configuration of the specialised-wave kernel for a layer: th = 0 -> not covered (the caller uses conv_lds_kernel)
-PcPlan conv_pc_plan(int dtype, int taps, int B, int H, int W, int Cin, int Cout, int force) {
-    PcPlan p{0, 0, 0, 0};
-    if ((dtype != CHORE_F16X3 && dtype != CHORE_F16 && dtype != CHORE_BF16) || Cin % 32 || Cout % 32) return p;
-    auto ring = [&](PcPlan& q) {   // taps per K-step and ring depth of a tiling (what fits 160 KB of LDS)
-        // (measured, profiles/r03_conv_phase_breakdown.txt: rings of single taps with 4 - 6 slots are no faster than two slots of
-        // whole kernel rows -- the consumers pay per K-step for the hand-over -- except where only single taps fit: 128 channels)
-        if (taps == 1) { q.tps = 1; q.nslot = 2; return; }
-        if (q.nt == 128) { q.tps = 1; q.nslot = 3; }
-        else if (q.th == 4 && q.nt == 32) { q.tps = 9; q.nslot = 2; }
-        else { q.tps = 3; q.nslot = 2; }
-    };
-    if (!force) {   // CHORE_PC_FORCE="taps,Cin,Cout,H:th*1000+nt[;...]" -- tiling experiments (scripts/conv_layer_ab.py)
-        static const char* env = getenv("CHORE_PC_FORCE");
-        if (env) {
-            const char* q = env;
-            while (*q) {
-                int t, ci, co, hh, f, n = 0;
-                if (sscanf(q, "%d,%d,%d,%d:%d%n", &t, &ci, &co, &hh, &f, &n) == 5 && t == taps && ci == Cin && co == Cout && hh == H) { force = f; break; }
-                while (*q && *q != ';') ++q;
-                if (*q == ';') ++q;
-            }
-        }
-    }
-    if (force) {   // development: th * 1000 + nt (e.g. 8064)
-        p.th = force / 1000; p.nt = force % 1000;
-        ring(p);
-        return p;
-    }
-    const long px_tiles8 = (long)B * ((H + 7) / 8) * (W / 32);
-    if (taps == 1) {
-        if (Cout % 128 == 0) { p.th = 8; p.nt = 128; }
-        else if (Cout % 64 == 0) { p.th = 8; p.nt = 64; }
-        else return p;
-        ring(p);
-        return p;
-    }
-    // 3x3: the widest channel tile that still gives every CU a workgroup; 4-row tiles when 8-row tiles leave CUs idle
-    if (Cout % 128 == 0 && px_tiles8 * (Cout / 128) >= 256) { p.th = 8; p.nt = 128; }
-    else if (Cout % 64 == 0 && px_tiles8 * (Cout / 64) >= 256) { p.th = 8; p.nt = 64; }
-    else if (px_tiles8 * (Cout / 32) >= 256) { p.th = 8; p.nt = 32; }
-    else if (H % 4 == 0 && Cout % 64 == 0 && px_tiles8 * 2 * (Cout / 64) >= 256) { p.th = 4; p.nt = 64; }
-    else if (H % 4 == 0) { p.th = 4; p.nt = 32; }
-    else { p.th = 8; p.nt = 32; }
-    ring(p);
-    return p;
-}
-
-int launch_conv_pc(chore_handle* h, int dtype, int taps, const PcPlan& p, const ConvArgs& a, hipStream_t s) {
-    if (a.res2.p) CHORE_FAIL(h, CHORE_EINVAL, "conv_pc: a second residual is not supported (conv_lds_kernel has it)");
-    chore_note_conv(h, CONV_FAM_PC, p.th, p.nt, p.tps, p.nslot, conv_note_flags(a), a.in.C);
-    const int key = ((taps * 10 + p.th) * 1000 + p.nt) * 100 + p.tps * 10 + p.nslot;
+// the plan's tiling (conv_plan.h: conv_pc_tile) -> its instantiation
+int launch_conv_pc(chore_handle* h, int dtype, int taps, const ConvLaunchPlan& p, const ConvArgs& a, hipStream_t s) {
+    const int key = ((taps * 10 + p.rows) * 1000 + p.nt) * 100 + p.tps * 10 + p.nslot;
 #define PC_CASE(TAPS, TH, NT, TPS, NSLOT) \
     case ((TAPS * 10 + TH) * 1000 + NT) * 100 + TPS * 10 + NSLOT:                                              \
         return dtype == CHORE_F16 ? launch_pc_t<h16_t, TAPS, TH, NT, TPS, NSLOT>(h, a, s) \
@@ -748,5 +699,5 @@ int launch_conv_pc(chore_handle* h, int dtype, int taps, const PcPlan& p, const 
         PC_CASE(1, 8, 64, 1, 2);
     }
 #undef PC_CASE
-    CHORE_FAIL(h, CHORE_EINVAL, "conv_pc: no kernel for taps=%d th=%d nt=%d tps=%d nslot=%d", taps, p.th, p.nt, p.tps, p.nslot);
+    CHORE_FAIL(h, CHORE_EINVAL, "conv_pc: no kernel for taps=%d th=%d nt=%d tps=%d nslot=%d", taps, p.rows, p.nt, p.tps, p.nslot);
 }

@@ -378,26 +378,7 @@ int launch_rw_t(chore_handle* h, const ConvArgs& a, hipStream_t s) {
 
 }  // namespace
 
-// CHORE_CONV_RW=0: the 1x1 layers stay on conv_pc_kernel (A/B runs)
-bool conv_rw_covers(int dtype, int taps, int Cin, int Cout, bool scaled_input) {
-    static const bool off = getenv("CHORE_CONV_RW") && atoi(getenv("CHORE_CONV_RW")) == 0;
-    // CHORE_CONV_RW_X3ONLY=1: the fp16 instantiation off (A/B against conv_pc_kernel in that mode).  bf16 is OPT-IN
-    // (CHORE_CONV_RW_BF16=1): alone the layers are faster (256 -> 256 at 128^2 24.8 against 36.2 us on conv_lds_kernel), inside the
-    // encoder they are not (12 launches: 0.399 against 0.376 ms per step; whole bf16 step 3.28 against 3.25 ms, profiles/r05_conv_rw.txt):
-    // conv_lds_kernel's many small workgroups hide a cold start (weights, statistics, instructions) that one persistent workgroup
-    // per CU pays in full on a 20 us kernel.
-    static const bool x3only = getenv("CHORE_CONV_RW_X3ONLY") != nullptr, bf16_on = getenv("CHORE_CONV_RW_BF16") != nullptr;
-    if (off || taps != 1 || (dtype != CHORE_F16X3 && dtype != CHORE_F16 && dtype != CHORE_BF16)) return false;
-    if (dtype == CHORE_F16 && x3only) return false;
-    if (dtype == CHORE_BF16 && !bf16_on) return false;
-    if (scaled_input) return dtype == CHORE_F16X3 && Cin == 256 && Cout == 256;     // data gradients of fp16 x 3 training: the stack tail's layers
-    return (Cin == 256 && Cout == 256) || (Cin == 128 && Cout == 256) || (Cin == 64 && Cout == 128);
-}
-bool conv_rw_eligible(int dtype, int taps, const ConvArgs& a) {
-    if (a.res2.p) return false;
-    return conv_rw_covers(dtype, taps, a.in.C, a.Cout, a.in_amax != nullptr);
-}
-
+// the shapes conv_plan.h (conv_rw_covers) sends here -> their instantiations
 template <typename T>
 static int launch_conv_rw_t(chore_handle* h, const ConvArgs& a, hipStream_t s) {
     const int k = a.in.C, n = a.Cout;
@@ -418,7 +399,6 @@ static int launch_conv_rw_t(chore_handle* h, const ConvArgs& a, hipStream_t s) {
 }
 
 int launch_conv_rw(chore_handle* h, int dtype, const ConvArgs& a, hipStream_t s) {
-    chore_note_conv(h, CONV_FAM_RW, 0, a.Cout, 1, 0, conv_note_flags(a), a.in.C);
     if (dtype == CHORE_F16) return launch_conv_rw_t<h16_t>(h, a, s);
     if (dtype == CHORE_BF16) return launch_conv_rw_t<bf16_t>(h, a, s);
     if (dtype == CHORE_F16X3) return launch_conv_rw_t<x3_t>(h, a, s);

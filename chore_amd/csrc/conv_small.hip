@@ -383,43 +383,14 @@ int launch_small_c(chore_handle* h, int rows, const ConvArgs& a, hipStream_t s) 
     CHORE_FAIL(h, CHORE_EINVAL, "conv_small: unsupported Cin=%d", a.in.C);
 }
 
-// rows per workgroup; 0 = use conv_lds_kernel.  Environment overrides for A/B measurements.
-int small_rows(int dtype, int H, int W, int Cin) {
-    static const int r32 = getenv("CHORE_CONV_SMALL_ROWS32") ? atoi(getenv("CHORE_CONV_SMALL_ROWS32")) : -1;
-    static const int r64 = getenv("CHORE_CONV_SMALL_ROWS64") ? atoi(getenv("CHORE_CONV_SMALL_ROWS64")) : -1;
-    static const int r64c = getenv("CHORE_CONV_SMALL_ROWS64_C256") ? atoi(getenv("CHORE_CONV_SMALL_ROWS64_C256")) : -1;
-    const bool x3 = dtype == CHORE_F16X3;
-    int rows;
-    if (H * W <= 32 * 32) rows = r32 >= 0 ? r32 : ((x3 || dtype == CHORE_F16) ? 2 : 1);
-    else if (Cin == 256) rows = r64c >= 0 ? r64c : 0;
-    else rows = r64 >= 0 ? r64 : 0;
-    // LDS: (rows + 2) x 34 pixels x (2 Cin + 16) bytes per plane, two planes for fp16 x 3
-    while (rows > 0 && (size_t)(x3 ? 2 : 1) * (rows + 2) * PW * (Cin * 2 + 16) + (size_t)Cin * 8 + 2048 > 160 * 1024) rows >>= 1;
-    if (rows && H % rows) rows = 0;
-    return rows;
-}
-
 }  // namespace
 
-// Where it is used (measured, bench.py encode time, B = 4: bf16 4.06 -> 3.79 ms, fp16 x 3 6.55 -> 6.1 ms).  A workgroup
-// fetches its K slice of the weights (147 KB for 256 -> 128 channels) and its halo patch from L2 on its own, so the
-// kernel trades L2 traffic for parallelism.  It wins on the 32 x 32 maps, where conv_lds_kernel has 16-64 workgroups for
-// 256 CUs.  On the 64 x 64 maps it loses in every variant tried (1, 2 or 4 rows per workgroup, CHORE_CONV_SMALL_ROWS64*):
-// 1 024-2 048 workgroups x 200 KB is L2-bandwidth bound (53 us against 26 us for the 256-channel convolution), and with
-// several rows per workgroup the waves drift apart and each pulls the weight fragments through the 32 KB L1 again --
-// sharing them takes the LDS ring and barriers of conv_lds_kernel, which therefore keeps those maps.  bf16 and
-// fp16 x 3 only: the native-fp32 parity mode keeps the one kernel it was validated with.
-bool conv_small_eligible(int dtype, int taps, int H, int W, int Cin, int Cout) {
-    static const bool off = getenv("CHORE_NO_CONV_SMALL") != nullptr;      // A/B switch
-    if (off || taps != 9 || (dtype != CHORE_BF16 && dtype != CHORE_F16X3 && dtype != CHORE_F16)) return false;
-    if (W % 32 || Cout % 32 || (Cin != 64 && Cin != 128 && Cin != 256) || H * W > 64 * 64) return false;
-    return small_rows(dtype, H, W, Cin) > 0;
-}
+static_assert(PW == CONV_SMALL_PW, "conv_plan.h sizes this kernel's patch with it");
 
-int launch_conv_small(chore_handle* h, int dtype, const ConvArgs& a, hipStream_t s) {
+// where it is used and with how many rows per workgroup: conv_plan.h (conv_small_eligible, conv_small_rows)
+int launch_conv_small(chore_handle* h, int dtype, const ConvLaunchPlan& p, const ConvArgs& a, hipStream_t s) {
     if ((size_t)a.B * a.H * (a.W / 32) * (a.Cout / 32) > 0x7fffffffull) CHORE_FAIL(h, CHORE_EINVAL, "conv_small: grid too large");
-    const int rows = small_rows(dtype, a.H, a.W, a.in.C);
-    chore_note_conv(h, CONV_FAM_SMALL, rows, 32, 9, 0, conv_note_flags(a), a.in.C);
+    const int rows = p.rows;
     if (dtype == CHORE_F16) return launch_small_c<h16_t>(h, rows, a, s);
     if (dtype == CHORE_F16X3 && a.in_amax) return launch_small_c<x3s_t>(h, rows, a, s);
     return dtype == CHORE_F16X3 ? launch_small_c<x3_t>(h, rows, a, s) : launch_small_c<bf16_t>(h, rows, a, s);

@@ -216,7 +216,7 @@ struct ConvArgs {
     // kernel multiplies the operand by the power of two that brings the maximum to 2^13 .. 2^14 before the hi / lo split (fp16
     // keeps 22 bits of a pair only above 2^-3) and the accumulators by its inverse.  NULL: operand taken as is.
     const unsigned* in_amax = nullptr;
-    // minimum number of workgroups the tiling of a small layer must yield (conv_mw_plan): 0 = a tile per CU (256).  The inference
+    // minimum number of workgroups the tiling of a small layer must yield (conv_plan.h, conv_mw_tile): 0 = a tile per CU (256).  The inference
     // encoder passes CONV_MW_FILL_INFER: half the CUs per launch, the other half for the other step in flight; training's operators
     // leave 0 (measured: 29.15 against 29.55 ms per step with the dense tiles, profiles/r06_conv_fill.txt)
     int fill = 0;
@@ -272,40 +272,20 @@ template <> struct Vec4<h16_t> {
 };
 #endif
 
-// the flag word of chore_handle::last_conv for a launch with these arguments
-inline int conv_note_flags(const ConvArgs& a, bool small_grid = false) {
-    return (a.in_amax ? CONV_FLAG_SCALED : 0) | (a.in_st ? CONV_FLAG_GN : 0) | (small_grid ? CONV_FLAG_SMALL_GRID : 0) |
-           (a.res.p ? CONV_FLAG_RES : 0) | (a.pool.p ? CONV_FLAG_POOL : 0);
+// what conv_launch_plan (conv_plan.h) needs to know of a launch's arguments besides the shape
+inline ConvTraits conv_traits_of(const ConvArgs& a) {
+    ConvTraits t;
+    t.gn = a.in_st != nullptr; t.scaled = a.in_amax != nullptr;
+    t.res = a.res.p != nullptr; t.res2 = a.res2.p != nullptr; t.pool = a.pool.p != nullptr; t.out = a.out.p != nullptr;
+    t.fill = a.fill;
+    t.st_raw_C = a.st_raw ? a.st_raw_C : 0; t.st_out_C = a.st_out ? a.st_out_C : 0; t.st_pool_C = a.st_pool ? a.st_pool_C : 0;
+    return t;
 }
-
-struct ConvPlan { int nt, th, ntiles, tps, small_cin; };   // N tile, tile height, tiles per image, taps per K-step (tps 0: conv_small_kernel)
-// small maps (conv_small.hip): one workgroup = 32 pixels of a row x 32 output channels, K split over its four waves
-bool conv_small_eligible(int dtype, int taps, int H, int W, int Cin, int Cout);
-int launch_conv_small(chore_handle* h, int dtype, const ConvArgs& a, hipStream_t s);
-ConvPlan conv_plan(int dtype, int taps, int B, int H, int W, int Cin, int Cout);   // tile configuration launch_conv will use
-
-// specialised-wave convolution (conv_pc.hip, fp16 x 3 operands): th rows x 32 pixels x nt channels per workgroup, tps taps per
-// K-step, nslot K-steps of weights resident in LDS; th = 0: the layer is not covered and launch_conv uses conv_lds_kernel
-struct PcPlan { int th, nt, tps, nslot; };
-PcPlan conv_pc_plan(int dtype, int taps, int B, int H, int W, int Cin, int Cout, int force = 0);
-int launch_conv_pc(chore_handle* h, int dtype, int taps, const PcPlan& p, const ConvArgs& a, hipStream_t s);
-bool conv_use_pc();
-// the same tilings with the staging work inside the MFMA-issuing waves (conv_mw.hip, round 6): four waves, one per SIMD, no producers
-constexpr int CONV_MW_FILL_INFER = 128;
-int conv_mw_fill(int asked);            // the `fill` a launch gets: CHORE_CONV_MW_FILL if set (every launch), else asked (0 -> 256)
-bool conv_mw_on(int dtype, int taps);   // by mode: fp16 x 3, 3x3, not switched off (CHORE_CONV_MW=0)
-PcPlan conv_mw_plan(int dtype, int taps, int B, int H, int W, int Cin, int Cout, int fill);   // conv_pc_plan's tiling, or one only this kernel has
-bool conv_mw_has(const PcPlan& p);      // an instantiation for this tiling exists
-bool conv_mw_covers(int dtype, int taps, const PcPlan& p, const ConvArgs& a);
-// a launch of this layer can carry a pooled output (ConvArgs::pool): by mode, taps, channels and even H and W -- never by the batch
-// size (one image alone and the same image inside a batch must take the same path).  Every tiling conv_mw_plan yields pools
-bool conv_mw_pool_covers(int dtype, int taps, int Cin, int Cout, int H, int W);
-// the same question for whichever kernel launch_conv picks (conv_mw_kernel only; the 1x1 layers keep the pooling pass: DESIGN section 4)
-bool conv_pool_covers(int dtype, int taps, int Cin, int Cout, int H, int W);
-int launch_conv_mw(chore_handle* h, int dtype, int taps, const PcPlan& p, const ConvArgs& a, hipStream_t s);
-// 1x1 layers (fp16 x 3, fp16, bf16) with register-resident weights (conv_rw.hip): persistent workgroups over runs of pixel blocks
-bool conv_rw_covers(int dtype, int taps, int Cin, int Cout, bool scaled_input);   // by shape (scaled_input: ConvArgs::in_amax set)
-bool conv_rw_eligible(int dtype, int taps, const ConvArgs& a);
+// launch_conv (conv_lds.hip) forms the plan of the launch, refuses what the plan refuses, notes the plan on the handle and hands it
+// to its family's launcher, which maps it to a template instantiation -- a plan without one is an error -- and computes grid and LDS
+int launch_conv_small(chore_handle* h, int dtype, const ConvLaunchPlan& p, const ConvArgs& a, hipStream_t s);
+int launch_conv_pc(chore_handle* h, int dtype, int taps, const ConvLaunchPlan& p, const ConvArgs& a, hipStream_t s);
+int launch_conv_mw(chore_handle* h, int dtype, int taps, const ConvLaunchPlan& p, const ConvArgs& a, hipStream_t s);
 int launch_conv_rw(chore_handle* h, int dtype, const ConvArgs& a, hipStream_t s);
 int launch_conv(chore_handle* h, int dtype, int taps /*1|9*/, const ConvArgs& a, hipStream_t s);
 size_t packed_conv_bytes(int dtype, int taps, int Cin, int Cout);

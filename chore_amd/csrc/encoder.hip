@@ -187,33 +187,10 @@ const char* const kclass_names[K_NUM] = {"stem_kernel", "gn_stats_kernel", "gn_a
                                          "conv_mw_kernel<T,9,8,128,1,3>", "conv_mw_kernel<T,9,8,64,3,2>", "conv_mw_kernel<T,9,8,32,3,2>",
                                          "conv_mw_kernel<T,9,4,64,3,2>", "conv_mw_kernel<T,9,4,32,9,2>", "conv_mw_kernel<T,9,2,128,1,3>",
                                          "conv_mw_kernel<T,9,4,128,1,3>", "conv_mw_kernel<T,9,2,64,1,3>"};
-inline int conv_class(const ConvPlan& p, int taps) {
-    if (p.tps == 0) return K_CONV_FIRST + 8 + (p.small_cin == 64 ? 0 : (p.small_cin == 128 ? 1 : 2));
-    const int ni = p.nt == 128 ? 0 : (p.nt == 64 ? 1 : 2);
-    if (taps == 1) return K_CONV_FIRST + 5 + ni;
-    if (p.tps == 9) return K_CONV_FIRST + 3 + (ni - 1);
-    return K_CONV_FIRST + ni;
-}
-// class of the kernel launch_conv will pick for a layer (the specialised-wave kernel where it covers the layer)
-inline int conv_class_of(int dtype, int taps, int B, int H, int W, int Cin, int Cout) {
-    if (conv_mw_on(dtype, taps)) {   // as launch_conv: conv_mw_kernel's own tiling first (it also takes the small maps, CHORE_CONV_MW_FILL)
-        const PcPlan mp = conv_mw_plan(dtype, taps, B, H, W, Cin, Cout, CONV_MW_FILL_INFER);
-        if (mp.th && conv_mw_has(mp) && (conv_mw_fill(CONV_MW_FILL_INFER) < 256 || !conv_small_eligible(dtype, taps, H, W, Cin, Cout))) {
-            if (mp.th == 8) return K_MW_FIRST + (mp.nt == 128 ? 0 : (mp.nt == 64 ? 1 : 2));
-            if (mp.th == 4) return K_MW_FIRST + (mp.nt == 128 ? 6 : (mp.nt == 64 ? 3 : 4));
-            return K_MW_FIRST + (mp.nt == 128 ? 5 : 7);
-        }
-    }
-    if (conv_rw_covers(dtype, taps, Cin, Cout, false) && conv_use_pc() && !conv_small_eligible(dtype, taps, H, W, Cin, Cout)) return K_RW;
-    if ((dtype == CHORE_F16 || (dtype == CHORE_F16X3 && conv_use_pc())) && !conv_small_eligible(dtype, taps, H, W, Cin, Cout)) {
-        const PcPlan pp = conv_pc_plan(dtype, taps, B, H, W, Cin, Cout);
-        if (pp.th) {
-            if (taps == 1) return K_PC_FIRST + (pp.nt == 128 ? 5 : 6);
-            if (pp.th == 8) return K_PC_FIRST + (pp.nt == 128 ? 0 : (pp.nt == 64 ? 1 : 2));
-            return K_PC_FIRST + (pp.nt == 64 ? 3 : 4);
-        }
-    }
-    return conv_class(conv_plan(dtype, taps, B, H, W, Cin, Cout), taps);
+static_assert(K_NUM - K_CONV_FIRST == CONV_PROFILE_CLASSES, "conv_profile_class (conv_plan.h) indexes the convolution classes above");
+// class of the kernel launch_conv will launch for a layer: the layer's plan, under the traits conv() knows
+inline int conv_class_of(int dtype, int taps, int B, int H, int W, int Cin, int Cout, const ConvTraits& t) {
+    return K_CONV_FIRST + conv_profile_class(conv_launch_plan(dtype, taps, B, H, W, Cin, Cout, t, conv_switches()), taps, Cin);
 }
 
 enum StepKind { S_KERNEL = 0, S_RECORD, S_WAIT, S_MEMSET };
@@ -382,7 +359,9 @@ struct Builder {
                     " cout=" + std::to_string(c.cout) + " HxW=" + std::to_string(c.in.H) + "x" + std::to_string(c.in.W);
         {
             const double px = (double)B * c.in.H * c.in.W;
-            cur_class = conv_class_of(dtype, c.taps, B, c.in.H, c.in.W, c.in_C, c.cout);
+            ConvTraits t;      // as the launch below fills its ConvArgs
+            t.gn = use_gn; t.res = c.has_res; t.res2 = c.has_res2; t.pool = c.has_pool; t.out = !c.no_out; t.fill = CONV_MW_FILL_INFER;
+            cur_class = conv_class_of(dtype, c.taps, B, c.in.H, c.in.W, c.in_C, c.cout, t);
             cur_flops = 2.0 * c.taps * c.in_C * c.cout * px;
             cur_bytes = px * es() * (c.in_C + c.cout * ((c.no_out ? 0.0 : 1.0) + (c.has_pool ? 0.25 : 0.0) + (c.has_raw ? 1 : 0) + (c.has_res ? 1 : 0) + (c.has_res2 ? 1 : 0)));
         }

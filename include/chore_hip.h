@@ -916,6 +916,16 @@ int chore_debug_last_wgrad(chore_handle* h, int* out, int n);
  *   out[5] points of a tile   out[6] threads of a workgroup   out[7] 1: the sort runs first (query_bin_kernel, query_perm_kernel)
  *   out[8] the kernel's T: the maps' type (CHORE_F32 float, CHORE_BF16 unsigned short, CHORE_F16 qh16_t) */
 int chore_query_plan(int op, int dtype, int B, int N, int FH, int FW, int live_mask, int flags, int switches, int* out, int n);
+/* which kernel and tiling a forward / data-gradient convolution launch gets (csrc/conv_plan.h; no handle, no device): what launch_conv
+ * decides for these arguments under this process's switches (CHORE_CONV_*, CHORE_NO_CONV_SMALL, CHORE_PC_FORCE: read once per process).
+ *   dtype, taps (1 | 9), B, H, W, Cin, Cout   the launch's mode and shape (Cin, Cout: of the launched convolution)
+ *   traits_bits  1 GroupNorm fused into the input, 2 scaled operand (the data gradient of CHORE_F16X3), 4 residual, 8 second residual,
+ *                16 pooled output, 32 `out` is written
+ *   fill         0, or 128 as the inference encoder asks (the least number of workgroups a small layer's tiling must yield)
+ * Writes min(n, 7) ints and returns that count, or CHORE_EINVAL for a bad argument and for what launch_conv refuses:
+ *   out[0..5]    as chore_debug_last_conv: kernel family, rows, channels per workgroup, taps per K-step, resident K-steps, flags
+ *   out[6]       the profile class of the launch in the encoder: the index among the conv_* classes of chore_profile_read */
+int chore_conv_plan(int dtype, int taps, int B, int H, int W, int Cin, int Cout, int traits_bits, int fill, int* out, int n);
 
 #ifdef __cplusplus
 }

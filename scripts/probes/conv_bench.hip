@@ -1,7 +1,8 @@
 // conv_bench.hip -- times single convolution layers of the encoder in isolation (development aid, not part of the library).
 //
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DCHORE_CONV_ABLATE=1 -I chore_amd/csrc \
-//         scripts/probes/conv_bench.hip chore_amd/csrc/conv_lds.hip chore_amd/csrc/conv_small.hip chore_amd/csrc/enc_misc.hip \
+//         scripts/probes/conv_bench.hip chore_amd/csrc/conv_lds.hip chore_amd/csrc/conv_small.hip chore_amd/csrc/conv_pc.hip \
+//         chore_amd/csrc/conv_mw.hip chore_amd/csrc/conv_rw.hip chore_amd/csrc/enc_misc.hip \
 //         -o scripts/probes/conv_bench
 //   scripts/probes/conv_bench [dtype=3] [iters=200]
 //
@@ -109,8 +110,9 @@ int main(int argc, char** argv) {
         if (sh.res) { a.res.p = dres; a.res.cs = 256; a.res.co = oco; a.res.C = sh.Cout; }
         a.st_out = st_out; a.st_out_C = 256; a.st_out_co = oco;
         a.B = B; a.H = sh.H; a.W = sh.W; a.Cout = sh.Cout;
-        const ConvPlan pl = conv_plan(dtype, sh.taps, B, sh.H, sh.W, sh.Cin, sh.Cout);
-        const int wgs = pl.tps == 0 ? -1 : B * pl.ntiles * (sh.Cout / pl.nt);
+        // (conv_switches() is read here for the first time: after the setenv above)
+        const ConvLaunchPlan pl = conv_launch_plan(dtype, sh.taps, B, sh.H, sh.W, sh.Cin, sh.Cout, conv_traits_of(a), conv_switches());
+        const int wgs = pl.family == CONV_FAM_SMALL ? -1 : B * (int)conv_lds_tiles(sh.H, sh.W) * (sh.Cout / pl.nt);
         unsigned long long* dticks;
         CK(hipMalloc(&dticks, 32 * 8));
         a.dbg_ticks = dticks;
@@ -119,7 +121,7 @@ int main(int argc, char** argv) {
         CK(hipEventCreate(&e1));
         const double gflop = 2.0 * sh.taps * sh.Cin * sh.Cout * (double)px * 1e-9;
         // variant 0 = conv_lds_kernel (or conv_small), then the forced tilings of conv_pc_kernel: th * 1000 + nt
-        // 1 = the tiling conv_pc_plan picks  (the persistent kernel of round 4, conv_pp.hip, was removed in round 6: slower on every
+        // 1 = the tiling conv_pc_tile picks  (the persistent kernel of round 4, conv_pp.hip, was removed in round 6: slower on every
         // layer, profiles/r04_conv_pp.txt; `git show b66b39a:chore_amd/csrc/conv_pp.hip` has it)
         const int forces9[] = {0, 1, 8128, 8064, 8032, 4064, 4032};
         const int forces1[] = {0, 1, 8128, 8064};
@@ -128,16 +130,18 @@ int main(int argc, char** argv) {
         const int nfl = sh.taps == 9 ? 7 : 4;
         for (int fi = 0; fi < nfl; ++fi) {
             const int force = fl[fi];
-            PcPlan pp{0, 0, 0, 0};
+            ConvTile pp{0, 0, 0, 0};
+            ConvLaunchPlan fp = pl;     // `force`: an override applied to the plan
             int vw = wgs;
             if (force > 0) {
-                pp = conv_pc_plan(dtype, sh.taps, B, sh.H, sh.W, sh.Cin, sh.Cout, force == 1 ? 0 : force);
+                pp = conv_pc_tile(dtype, sh.taps, B, sh.H, sh.W, sh.Cin, sh.Cout, conv_switches(), force == 1 ? 0 : force);
                 if (!pp.th || sh.Cout % pp.nt || sh.H % pp.th) continue;
                 vw = B * (sh.H / pp.th) * (sh.W / 32) * (sh.Cout / pp.nt);
+                fp.family = CONV_FAM_PC; fp.rows = pp.th; fp.nt = pp.nt; fp.tps = pp.tps; fp.nslot = pp.nslot;
             }
             auto run = [&](int dbg) -> int {
                 a.dbg = dbg | (1 << 30);
-                return force ? launch_conv_pc(h, dtype, sh.taps, pp, a, s) : launch_conv(h, dtype, sh.taps, a, s);
+                return force ? launch_conv_pc(h, dtype, sh.taps, fp, a, s) : launch_conv(h, dtype, sh.taps, a, s);
             };
             // correctness against variant 0 (same arithmetic, another summation order over the chunks)
             CK(hipMemsetAsync(dout, 0, nout * esz, s));

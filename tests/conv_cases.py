@@ -6,9 +6,9 @@ and map size, and a kind:
   "plain"  forward without GroupNorm, inputs and weights in {-1, 0, 1}            -> compared bit for bit
   "bwd"    data gradient (chore_conv2d_bwd_data: dy has `cin` channels, dx `cout`; the layer's weight is (cin, cout, k, k)),
            inputs and weights in {-1, 0, 1}                                        -> compared bit for bit
-The shapes were chosen by reading the planners (conv_pc_plan, conv_mw_plan, small_rows, conv_rw_covers, choose_nt,
-is_small_grid); which kernel each one reaches is not asserted per case but through COVERAGE: every row marked covered must
-have been reported by chore_debug_last_conv for at least one case of the run.
+The shapes were chosen by reading the planners (csrc/conv_plan.h: conv_pc_tile, conv_mw_tile, conv_small_rows, conv_rw_covers, conv_lds_nt,
+conv_lds_small_grid); which kernel each one reaches is pinned job by job in tests/conv_plan_cases.py (EXPECTED) and summed up in
+COVERAGE: every row marked covered must have been reported by chore_debug_last_conv for at least one case of the run.
 
 A coverage key names one template instantiation a launcher can pick:
   ("pc", dtype, taps, th, nt, tps, nslot)     conv_pc_kernel, the PC_CASE lines;   dtype: "fp16", "bf16", "x3", "x3s"
@@ -97,7 +97,7 @@ SWITCH_SETS = {
     "pc_bf16": ({"CHORE_CONV_PC_BF16": "1"}, ("bf16",), None, None, None),
     "lds_bf16": ({"CHORE_CONV_LDS_BF16": "1"}, ("bf16",), None, None, None),
     "rw_bf16": ({"CHORE_CONV_RW_BF16": "1"}, ("bf16",), (1,), None, None),
-    # an experiment switch, cheap to cover: conv_pc_plan never picks 4 x 32 x 64 by itself (its condition equals the one of
+    # an experiment switch, cheap to cover: conv_pc_tile never picks 4 x 32 x 64 by itself (its condition equals the one of
     # 8 x 32 x 32, which is tested first), CHORE_PC_FORCE puts the 64 -> 64 layers of the 64^2 map on it
     "pc_force": ({"CHORE_CONV_MW": "0", "CHORE_PC_FORCE": "9,64,64,64:4064"}, ("bf16", "x3", "fp16"), (9,), None, ("m64_64", "m64_64r")),
 }
@@ -145,7 +145,7 @@ PC_TILINGS = [(9, 8, 128, 1, 3), (9, 8, 64, 3, 2), (9, 8, 32, 3, 2), (9, 4, 64, 
 MW_TILINGS = [(8, 128, 1, 3), (4, 128, 1, 3), (2, 128, 1, 3), (2, 64, 1, 3), (8, 64, 3, 2), (8, 32, 3, 2), (4, 64, 3, 2), (4, 32, 9, 2)]
 RW_SHAPES = [(256, 256), (128, 256), (64, 128)]
 SMALL_ROWS = (1, 2, 4)
-SMALL_DEFAULT_ROWS = {"bf16": 1, "x3": 2, "fp16": 2, "x3s": 2}       # small_rows() of a process without CHORE_CONV_SMALL_ROWS*
+SMALL_DEFAULT_ROWS = {"bf16": 1, "x3": 2, "fp16": 2, "x3s": 2}       # conv_small_rows() of a process without CHORE_CONV_SMALL_ROWS*
 
 
 def _coverage():
@@ -171,7 +171,7 @@ def _coverage():
             t[("lds", dt, 1, nt, False)] = None
             t[("lds", dt, 9, nt, False)] = None
         t[("lds", dt, 9, 32, True)] = None
-        t[("lds", dt, 9, 64, True)] = ("unreachable: choose_nt returns 64 only from 448 workgroups on, the small-grid variant needs "
+        t[("lds", dt, 9, 64, True)] = ("unreachable: conv_lds_nt returns 64 only from 448 workgroups on, the small-grid variant needs "
                                        "fewer than 384")
     for dt in ("x3", "x3s"):
         for taps in (1, 9):

@@ -22,6 +22,17 @@ def test_library_exports_every_declared_symbol():
     assert _lib.lib.chore_version() >= 100
 
 
+def test_conv_plan_without_gpu():
+    """chore_conv_plan takes no handle and no device: family, tiling, flags and profile class of a launch, CHORE_EINVAL for what
+    launch_conv refuses (tests/test_conv_plan_host.py pins it case by case)"""
+    from chore_amd import _lib
+    out = (ctypes.c_int * 8)()
+    assert _lib.lib.chore_conv_plan(_lib.F32, 9, 4, 128, 128, 256, 128, 1 | 32, 0, out, 8) == 7      # GroupNorm-fused, `out` written
+    assert list(out[:7]) == [1, 8, 64, 3, 2, 2, 1]                                                    # conv_lds_kernel<float, 9, 64, 3>
+    assert _lib.lib.chore_conv_plan(_lib.F32, 9, 4, 128, 128, 250, 128, 1 | 32, 0, out, 8) == -1
+    assert _lib.lib.chore_conv_plan(_lib.F32, 9, 4, 128, 128, 256, 128, 1 | 32, 0, out, 0) == -1
+
+
 def test_sizes_without_gpu():
     from chore_amd import _lib
     cfg = _lib.EncoderCfg(5, 5, 2, 256)

@@ -5,7 +5,8 @@ Cases (tests/conv_cases.py) go through chore_conv2d_fwd / chore_conv2d_bwd_data.
 process, so every switch set runs in a child process of its own (this file with --child); the parent makes the inputs on the
 CPU with fixed seeds and hands them over in an .npz, so device and reference see the same bits, and a layer's reference is
 computed once and reused across the switch sets.  A child returns, per case and mode, the output buffer, the statistics cells
-of the output and the chore_debug_last_conv record (which kernel and tiling the launch chose).
+of the output, the chore_debug_last_conv record (which kernel and tiling the launch chose) and what chore_conv_plan says of the
+same arguments in that process: the two must agree for every job.
 
 Checks per case
   a. values, random input through GroupNorm ("gn"): fp32 and fp16 x 3 within 2e-5 of the reference's largest entry; bf16 within
@@ -57,6 +58,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import conv_cases as cc      # noqa: E402
+import conv_plan_cases as pcs  # noqa: E402
 import conv_ref              # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -196,6 +198,9 @@ def child_main(in_path, job_path, out_path):
         key = cid + "|" + mode
         out[key + "|y"] = (buf if tdt == torch.float32 else buf.view(torch.int16)).cpu().numpy()
         out[key + "|rec"] = rec
+        plan = (ctypes.c_int * 8)()
+        assert L.chore_conv_plan(*pcs.plan_args(c, mode), plan, 8) == 7, (cid, mode)
+        out[key + "|plan"] = np.array(list(plan)[:7], np.int64)
         if c["kind"] != "bwd":
             out[key + "|st"] = sty.cpu().numpy().view(np.int64)
     np.savez(out_path, **out)
@@ -263,6 +268,10 @@ def check_job(case, mode, res, worst):
     rec = res[key + "|rec"]
     wkey = cc.witness_key(case, mode, rec)
     fails = []
+    # the launch is the plan's (chore_conv_plan in the child, under its switches): family, tiling and flags, and the class that names them
+    plan = res[key + "|plan"]
+    if not (np.array_equal(rec[:6], plan[:6]) and int(rec[6]) == case["cin"] and pcs.CLASS_NAMES[int(plan[6])] == pcs.class_name(case, rec)):
+        fails.append("launched %r, chore_conv_plan says %r" % (list(rec[:7]), list(plan)))
     buf = as_float64(raw, mode)
     # c. every output written, nothing else
     if not (np.array_equal(buf[:margin], np.full(margin, SENTINEL)) and np.array_equal(buf[margin + n:], np.full(margin, SENTINEL))):

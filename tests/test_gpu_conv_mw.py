@@ -3,8 +3,8 @@ inside the MFMA-issuing waves -- against conv_pc_kernel, the specialised-wave ke
 
 The kernel choice is an environment switch the library reads once per process (CHORE_CONV_MW=0: conv_pc_kernel everywhere, =all:
 conv_mw_kernel on every tiling it has), so each variant runs in a process of its own and the results are compared here:
-  * single layers through chore_conv2d_fwd at every tiling conv_pc_plan has (8 x 32 x 128 / 64 / 32, 4 x 32 x 64 / 32; CHORE_CONV_MW_FILL=256
-    keeps conv_mw_plan on them), whole and ragged maps: the two
+  * single layers through chore_conv2d_fwd at every tiling conv_pc_tile has (8 x 32 x 128 / 64 / 32, 4 x 32 x 64 / 32; CHORE_CONV_MW_FILL=256
+    keeps conv_mw_tile on them), whole and ragged maps: the two
     kernels add the same products to the same accumulators in the same order, so the OUTPUT must be equal BIT FOR BIT; the GroupNorm
     statistics of the output are reduced from different partial sums (256 instead of 512 threads): equal to fp32 summation order;
   * the whole encoder (every stack's feature map, tmpx, normx), residual and raw-copy paths included: the statistics' last bits move
@@ -29,7 +29,7 @@ from chore_amd import _lib
 dev = torch.device("cuda", 0); h = _lib.handle(0); dt = _lib.F16X3
 stream = torch.cuda.current_stream().cuda_stream
 out = {{}}
-# (Cin, Cout, B, H, W): every tiling of conv_pc_plan, maps that end inside a tile, one and many chunks
+# (Cin, Cout, B, H, W): every tiling of conv_pc_tile, maps that end inside a tile, one and many chunks
 for n, (cin, cout, B, H, W) in enumerate([(256, 128, 4, 128, 128), (256, 128, 2, 40, 56), (128, 64, 4, 128, 128), (64, 64, 4, 128, 128),
                                           (64, 32, 2, 128, 128), (32, 32, 2, 256, 256), (256, 128, 4, 64, 64), (128, 64, 4, 64, 64),
                                           (64, 64, 4, 64, 64), (128, 64, 3, 20, 28), (64, 64, 3, 20, 28), (128, 128, 2, 64, 64)]):
@@ -86,7 +86,7 @@ def test_layers_equal_conv_pc_bit_for_bit(tmp_path):
         ya, yb = a["y%d" % i], b["y%d" % i]
         assert np.isfinite(ya).all() and np.abs(ya).max() > 0.1
         if i == 6:
-            # 256 -> 128 at 64^2, B = 4: with CHORE_CONV_MW_TH2 conv_mw_plan tiles it 2 x 32 pixels x 128 channels (conv_pc_plan: 8 x 32 x 32); the order
+            # 256 -> 128 at 64^2, B = 4: with CHORE_CONV_MW_TH2 conv_mw_tile tiles it 2 x 32 pixels x 128 channels (conv_pc_tile: 8 x 32 x 32); the order
             # in which a tile walks the 32-channel chunks depends on the tile's index, so the sums differ in their rounding
             assert np.abs(ya - yb).max() <= 2e-6 * np.abs(yb).max(), np.abs(ya - yb).max()
             assert not np.array_equal(ya, yb)
@@ -96,7 +96,7 @@ def test_layers_equal_conv_pc_bit_for_bit(tmp_path):
         assert np.abs(sa - sb).max() <= 2e-6 * np.abs(sb).max(), (i, np.abs(sa - sb).max(), np.abs(sb).max())
     # the switch did something: at least one layer's statistics differ in their last bits
     assert any(not np.array_equal(a["s%d" % i], b["s%d" % i]) for i in range(n))
-    # dense tilings (what the inference encoder asks for, ConvArgs::fill = 128): where conv_mw_plan picks another tile the chunk order differs, hence the rounding; same values otherwise
+    # dense tilings (what the inference encoder asks for, ConvArgs::fill = 128): where conv_mw_tile picks another tile the chunk order differs, hence the rounding; same values otherwise
     other = 0
     for i in range(n):
         yc, yb = c["y%d" % i], b["y%d" % i]

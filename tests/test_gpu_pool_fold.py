@@ -28,10 +28,10 @@ pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# (taps, Cin, Cout, B, H, W): the smallest maps that reach each tiling (conv_mw_plan), whole and -- where the plan allows it: the
+# (taps, Cin, Cout, B, H, W): the smallest maps that reach each tiling (conv_mw_tile), whole and -- where the plan allows it: the
 # eight-row tiles -- ending inside a tile in both directions with even H and W.  The four-row tiles of 64 and 128 channels come from
 # the dense plan only, which takes whole maps (H % 4 == 0, W % 32 == 0)
-CASES_256 = [  # CHORE_CONV_MW_FILL=256, a tile per CU: conv_pc_plan's tilings
+CASES_256 = [  # CHORE_CONV_MW_FILL=256, a tile per CU: conv_pc_tile's tilings
     (9, 256, 128, 2, 40, 56),     # too few tiles for the wide tilings: 4 x 32 x 32 (not one of the five; pools all the same), ragged
     (9, 128, 64, 3, 20, 28),
     (9, 64, 64, 3, 20, 28),
@@ -47,7 +47,7 @@ CASES_DENSE = [  # CHORE_CONV_MW_FILL=16: the widest tile that yields 16 workgro
     (9, 32, 128, 2, 32, 64),      # 8 x 32 x 128: 2 * 4 * 2 = 16
     (9, 32, 128, 2, 16, 64),      # 4 x 32 x 128: eight rows give 8 workgroups, four rows 16
     (9, 64, 64, 2, 16, 32),       # 2 x 32 x 64 (not one of the five)
-    (9, 256, 128, 2, 40, 56),     # W not a multiple of 32: conv_pc_plan's tiling, ragged
+    (9, 256, 128, 2, 40, 56),     # W not a multiple of 32: conv_pc_tile's tiling, ragged
     (9, 32, 64, 4, 16, 32),       # 4 x 32 x 64: 4 * 4 * 1 = 16
     (9, 64, 64, 4, 16, 32),       # 4 x 32 x 64, two chunks
 ]
