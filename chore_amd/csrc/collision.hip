@@ -15,7 +15,7 @@
 //                         share a vertex index dropped at once (13 of ~25 box neighbours of a triangle); a lane collects
 //                         its hits as a bit mask and a wave reserves list space with ONE atomic (a returning atomic
 //                         per hit is a dependent ~1.5 us chain: 100 us per dense tile); survivors -> candidate list
-//   coll_narrow_kernel    one thread per candidate: shared-position test, 17-axis separating-axis test -> pair list
+//   coll_narrow_kernel    one thread per candidate: shared-position test, zero-area test, 17-axis separating-axis test -> pair list
 //   coll_loss_kernel      one thread per pair: the two conic distance fields, value AND gradient w.r.t. the 18
 //                         coordinates by forward-mode dual numbers (exactly the derivative of the evaluated expression);
 //                         accumulated with 64-bit fixed-point atomics (integer adds commute: the result does not depend
@@ -243,6 +243,7 @@ __global__ __launch_bounds__(256) void coll_narrow_kernel(const float* __restric
         const V3 e1[3] = {sub(t1[1], t1[0]), sub(t1[2], t1[1]), sub(t1[0], t1[2])};
         const V3 e2[3] = {sub(t2[1], t2[0]), sub(t2[2], t2[1]), sub(t2[0], t2[2])};
         const V3 n1 = cross(e1[0], e1[1]), n2 = cross(e2[0], e2[1]);
+        if (dot(n1, n1) == 0.f || dot(n2, n2) == 0.f) continue;      // no area: no cone, no interior, no pair (oracle: find_collisions)
         bool sep = separates(n1, t1, t2) || separates(n2, t1, t2);
 #pragma unroll
         for (int p = 0; p < 3; ++p)

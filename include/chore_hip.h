@@ -587,7 +587,9 @@ int chore_prep_train_compose(chore_handle* h, const unsigned char* rgb, const un
  *   verts  (B,V,3) fp32: the concatenated mesh (SMPL vertices, then object vertices), faces (F,3) int32 into it.
  *   loss   (B) per-batch-element sums over all intersecting, non-adjacent triangle pairs (the caller takes the mean,
  *          like torch.mean(self.pen_distance(...)) :623);  gverts (B,V,3) = d loss[b] / d verts[b], kept for backward;
- *   counts (B+2 int32, or NULL): pairs found per batch element, then candidates / pairs dropped for lack of list space.
+ *          A triangle whose normal is exactly zero in fp32 has no cone and no interior: it takes part in no pair.
+ *   counts (B+2 int32, or NULL): pairs kept per batch element, then candidates / pairs dropped for lack of list space
+ *          (24 F + 4096 candidates, 8 F + 1024 pairs per element; which ones survive a full list is not defined).
  * chore_collision_bwd: dverts = gout[b] * gverts.  No host synchronisation, fixed launch grids (hipGraph-capturable),
  * fixed-point accumulation (bit-reproducible).
  * ------------------------------------------------------------------------------------------- */

@@ -16,6 +16,7 @@ package implements --
     coplanar triangles of a flat object face are not reported); the package finds the candidates with a
     BVH over the triangle bounding boxes and keeps at most `max_collisions` candidates per query triangle, in BVH
     traversal order; this restatement (and the HIP kernel) report EVERY intersecting pair, once, as (i, j), i < j;
+    a triangle whose normal (e0 x e1) is exactly zero takes part in no pair (its circumcircle and cone do not exist);
   * penetration measure: the conic distance fields of Tzionas et al., "Capturing Hands in Action using Discriminative
     Salient Points and Physics Simulation", IJCV 2016, eq. 13-15 (after Ballan et al. 2012): for a triangle f with
     circumcentre o_f, circumradius r_f and unit normal n_f, and a point v with x = n_f . (v - o_f),
@@ -63,11 +64,15 @@ def find_collisions(tris):
     """(F,3,3) -> (P,2) int64 array of intersecting pairs (i < j), lexicographic order"""
     tris = np.asarray(tris)
     lo, hi = tris.min(1), tris.max(1)
+    n = np.cross(tris[:, 1] - tris[:, 0], tris[:, 2] - tris[:, 1])
+    flat = (n * n).sum(-1) == 0          # a triangle without area has no cone and no interior: it forms no pair
     out = []
     for i in range(len(tris)):
+        if flat[i]:
+            continue
         cand = np.nonzero(((lo[i] <= hi[i + 1:]) & (lo[i + 1:] <= hi[i])).all(-1))[0] + i + 1
         for j in cand:
-            if not share_vertex(tris[i], tris[j]) and tri_tri_sat(tris[i], tris[j]):
+            if not flat[j] and not share_vertex(tris[i], tris[j]) and tri_tri_sat(tris[i], tris[j]):
                 out.append((i, int(j)))
     return np.asarray(out, dtype=np.int64).reshape(-1, 2)
 
