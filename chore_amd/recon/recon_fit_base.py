@@ -391,6 +391,40 @@ class ReconFitterBase:
                 frame = {k: None if v is None else {n: x[i] for n, x in v.items()} for k, v in rep.items()}
                 with open(sf.replace(".smpl.ply", ".penetration.json"), "w") as f:
                     json.dump(frame, f, indent=1)
+        if self.REPORT_OCCLUSION:               # of the very meshes written above; draws no random numbers
+            from .eval.occlusion import COUNT_KEYS, frame_report
+            if smpl.faces is None:
+                raise RuntimeError("REPORT_OCCLUSION needs the body model's faces")
+            dev = self.device
+            rep = self._occlusion_of(torch.as_tensor(verts, device=dev), smpl.faces, torch.as_tensor(obj_verts, device=dev))
+            counts = [rep[k].cpu().tolist() for k in COUNT_KEYS]
+            for i, sf in enumerate(smpl_files):
+                with open(sf.replace(".smpl.ply", ".occlusion.json"), "w") as f:
+                    json.dump(frame_report(*[c[i] for c in counts]), f, indent=1)
+
+    # ---- how much of the fitted object the fitted body hides (recon/eval/occlusion.py) --------------------------
+    # The reference skips a frame whose object is less than 30 % visible (recon/evaluate.py:53-58) and reads that from mask
+    # files of the dataset.  Here it comes from the fit's own meshes through the Kinect colour camera.
+    # True: save_outputs also writes k{test_id}.occlusion.json (one frame's counts, fractions and object_evaluated) next to
+    # the PLY files.  The fit itself never reads it: no fitted bit changes.
+    REPORT_OCCLUSION = False
+
+    def _occlusion_of(self, smpl_verts, smpl_faces, obj_verts):
+        from .eval.occlusion import occlusion
+        if self.scan_faces is None:
+            raise RuntimeError("occlusion_report needs the object template mesh (scan_verts / scan_faces)")
+        return occlusion(smpl_verts, smpl_faces, obj_verts, self.scan_faces)
+
+    def occlusion_report(self, smpl_verts, smpl_faces, obj_R, obj_t, obj_s):
+        """the arguments of penetration_report -> per-frame device tensors body_visible / body_full / object_visible /
+        object_full (int64 pixels of the frame), body_fraction / object_fraction (float64, NaN where nothing is covered):
+        recon/eval/occlusion.py.  No gradient."""
+        if self.scan_verts is None:
+            raise RuntimeError("occlusion_report needs the object template mesh (scan_verts / scan_faces)")
+        with torch.no_grad():
+            scan = self.scan_verts.unsqueeze(0).expand(obj_R.shape[0], -1, -1)
+            verts = self.transform_obj_verts(scan, obj_R.detach(), obj_t.detach(), obj_s.detach())
+        return self._occlusion_of(smpl_verts.detach(), smpl_faces, verts)
 
     # ---- how far the fitted meshes sit inside each other (recon/eval/penetration.py) ------------------------
     # Not in the reference.  An exact measure, independent of the interpenetration term, of what that term is there to reduce:

@@ -1,4 +1,5 @@
 """the names `import neural_renderer as nr` gives the reference's visualisation code (utils/render_utils.py)"""
 from ..recon.obj_pose_roi import projection, vertices_to_faces  # noqa: F401
-from .renderer import (Renderer, face_light, get_points_from_angles, lighting, look, look_at, perspective,  # noqa: F401
-                       rasterize_rgbad, rasterize_scene, splat_points, world_radius_to_pixels)
+from .renderer import (Renderer, face_light, face_visibility, get_points_from_angles, lighting, look, look_at,  # noqa: F401
+                       perspective, rasterize_instances, rasterize_rgbad, rasterize_scene, splat_points,
+                       world_radius_to_pixels)

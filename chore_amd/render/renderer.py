@@ -9,7 +9,9 @@ the vertical flip and the 2x2 anti-aliasing average are one call into libchore_h
 Differentiable like the reference's: when grad mode is on and the vertices, the textures or the light require grad, the
 rasterisation goes through `_RasterizeRGBAD` (chore_render_fwd + chore_render_bwd) and `render`, `render_rgb`, `render_depth`,
 `render_silhouettes` and `rasterize_rgbad` carry gradients; otherwise the call is the plain forward.  The point and scene
-renderers (`splat_points`, `rasterize_scene`, `render_points`, `render_scene`) are forward only and detach their inputs.
+renderers (`splat_points`, `rasterize_scene`, `render_points`, `render_scene`) are forward only and detach their inputs, and so
+are visibility and instance masks (`face_visibility`, `rasterize_instances`, `Renderer.visibility`, `Renderer.render_instances`:
+chore_instances_fwd; the reference's visibility.py:12-34 and renderer.py:79-117).
 
 Kept quirks of the reference: `light_direction` is used un-normalised; face normals are
 normalize(cross(v0 - v1, v2 - v1), eps=1e-5), dividing by max(norm, eps); lighting sees the world vertices, before the camera.
@@ -361,6 +363,64 @@ def rasterize_scene(faces, textures, light, points_ndc, colors=None, radius=2.0,
     return out
 
 
+MAX_GROUPS = 8        # chore_instances_fwd keeps an 8-bit cover mask per sample
+
+
+def rasterize_instances(faces, face_group=None, num_groups=1, image_size=256, anti_aliasing=True, near=DEFAULT_NEAR,
+                        far=DEFAULT_FAR, return_index=False):
+    """which group of faces owns a pixel, and which groups would cover it alone, in one walk (chore_instances_fwd; the rule is
+    written down in include/chore_hip.h).  faces (B,F,3,3) projected triangles as `rasterize_rgbad` takes them; face_group
+    (B,F) integers or None = every face in group 0; num_groups G in 1..8.  A face whose group lies outside 0..G-1 is an
+    occluder: it hides what is behind it and belongs to no group.
+    -> dict(visible (B,G,S,S): coverage of the group as seen; full (B,G,S,S): its coverage with every other face taken away;
+    face_samples (B,F) int32: samples each face wins; group_samples (B,G,2) int32: samples of visible / full
+    [, face_index (B,S*ssaa,S*ssaa) int32, rows not flipped]).  Forward only: the inputs are detached."""
+    if not faces.is_cuda:
+        raise RuntimeError("chore_amd needs device tensors (no CPU path)")
+    G = int(num_groups)
+    if not 1 <= G <= MAX_GROUPS:
+        raise ValueError("num_groups must lie in 1..%d, got %r" % (MAX_GROUPS, num_groups))
+    dev = faces.device
+    tri = faces.detach().float().contiguous()
+    if tri.dim() != 4 or tuple(tri.shape[2:]) != (3, 3):
+        raise ValueError("faces (B,F,3,3) expected, got %s" % (tuple(tri.shape),))
+    B, Fn = tri.shape[:2]
+    grp = None
+    if face_group is not None:
+        if torch.is_floating_point(face_group) or tuple(face_group.shape) != (B, Fn):
+            raise ValueError("face_group: integers %s expected, got %s %s" % ((B, Fn), face_group.dtype, tuple(face_group.shape)))
+        grp = face_group.detach().to(dev).to(torch.int32).contiguous()
+    ssaa, S = (2 if anti_aliasing else 1), int(image_size)
+    h = _lib.handle(dev.index or 0)
+    nbytes = _lib.lib.chore_instances_workspace_bytes(B, Fn, G, S, ssaa)
+    if nbytes == 0:
+        raise ValueError("unsupported instances shape B=%d F=%d G=%d image_size=%d ssaa=%d" % (B, Fn, G, S, ssaa))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    visible = torch.empty(B, G, S, S, dtype=torch.float32, device=dev)
+    full = torch.empty(B, G, S, S, dtype=torch.float32, device=dev)
+    face_samples = torch.empty(B, Fn, dtype=torch.int32, device=dev)
+    group_samples = torch.empty(B, G, 2, dtype=torch.int32, device=dev)
+    fim = torch.empty(B, S * ssaa, S * ssaa, dtype=torch.int32, device=dev) if return_index else None
+    _lib.check(_lib.lib.chore_instances_fwd(h, tri.data_ptr(), grp.data_ptr() if grp is not None else None, B, Fn, G, S, ssaa,
+                                            float(near), float(far), visible.data_ptr(), full.data_ptr(),
+                                            face_samples.data_ptr(), group_samples.data_ptr(),
+                                            fim.data_ptr() if return_index else None, ws.data_ptr(),
+                                            torch.cuda.current_stream(dev).cuda_stream), h, "chore_instances_fwd")
+    out = {"visible": visible, "full": full, "face_samples": face_samples, "group_samples": group_samples}
+    if return_index:
+        out["face_index"] = fim
+    return out
+
+
+def face_visibility(faces, image_size, near=DEFAULT_NEAR, far=DEFAULT_FAR, eps=1e-4):
+    """visibility.py:12-34 with its signature: faces (B,F,3,3) projected triangles -> (B,F) int32, 1 where the face wins at
+    least one pixel of the image_size grid (no anti-aliasing).  `eps` is accepted and not read, as in the reference."""
+    if not faces.is_cuda:
+        raise RuntimeError("chore_amd needs device tensors (no CPU path)")
+    out = rasterize_instances(faces, None, 1, image_size, False, near, far)
+    return (out["face_samples"] > 0).to(torch.int32)
+
+
 def world_radius_to_pixels(world_radius, z, focal_px):
     """pixel radius of a sphere of `world_radius` metres at depth z under a focal length of `focal_px` OUTPUT pixels:
     focal_px * world_radius / z, so points shrink with distance"""
@@ -412,7 +472,9 @@ class Renderer(nn.Module):
             return self.render_silhouettes(vertices, faces, K, R, t, dist_coeffs, orig_size)
         if mode == "depth":
             return self.render_depth(vertices, faces, K, R, t, dist_coeffs, orig_size)
-        raise ValueError("mode should be one of None, 'rgb', 'silhouettes' or 'depth'")
+        if mode == "visibility":
+            return self.visibility(vertices, faces, K, R, t, dist_coeffs, orig_size)
+        raise ValueError("mode should be one of None, 'rgb', 'silhouettes', 'depth' or 'visibility'")
 
     def transform(self, vertices, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
         """world vertices (B,V,3) -> [u, v in [-1,1], depth] under the camera mode (renderer.py:254-276)"""
@@ -474,6 +536,30 @@ class Renderer(nn.Module):
 
     def render_silhouettes(self, vertices, faces, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
         return self._rasterize(vertices, faces, None, (K, R, t, dist_coeffs, orig_size))["alpha"]
+
+    def _project_faces(self, vertices, faces, cam, face_group=None):
+        """projected triangles of a mesh, detached, with both windings (and their groups) when fill_back is set"""
+        faces = faces.detach()
+        if self.fill_back:
+            faces = torch.cat((faces, faces.flip(-1)), dim=1)
+            if face_group is not None:
+                face_group = torch.cat((face_group, face_group), dim=1)
+        return vertices_to_faces(self.transform(vertices.detach().float(), *cam), faces), face_group
+
+    def visibility(self, vertices, faces, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
+        """-> (B,F) int32, (B,2F) with fill_back: 1 where the face wins a pixel (renderer.py:84-117).  Like the reference it
+        rasterises at image_size without anti-aliasing, whatever self.anti_aliasing says.  Forward only."""
+        tri, _ = self._project_faces(vertices, faces, (K, R, t, dist_coeffs, orig_size))
+        return face_visibility(tri, self.image_size, near=self.near, far=self.far)
+
+    def render_instances(self, vertices, faces, face_group=None, num_groups=1, K=None, R=None, t=None, dist_coeffs=None,
+                         orig_size=None):
+        """the camera path of `render`, then `rasterize_instances`: face_group (B,F) integers per face of `faces` (both windings
+        get them under fill_back) or None -> its dict (face_samples is (B,2F) under fill_back).  Forward only."""
+        if face_group is not None:
+            face_group = torch.as_tensor(face_group).to(vertices.device)
+        tri, face_group = self._project_faces(vertices, faces, (K, R, t, dist_coeffs, orig_size), face_group)
+        return rasterize_instances(tri, face_group, num_groups, self.image_size, self.anti_aliasing, self.near, self.far)
 
     def focal_pixels(self, K=None, orig_size=None):
         """focal length in pixels of THIS renderer's output: K[0,0] scaled from `orig_size` to image_size in projection

@@ -205,6 +205,15 @@ class NrWrapper:
                                               face_group=mesh_face_group(meshes, self.device, used) if face_layers > 1 else None)
         return rgb[0].permute(1, 2, 0).clamp(0, 1).cpu().numpy(), alpha[0].cpu().numpy()
 
+    def render_masks(self, renderer, meshes):
+        """the mask of every mesh as seen and alone, in ONE instances call (Renderer.render_instances; the mesh index is the
+        face group, `mesh_face_group`): meshes with .v / .f, at most 8
+        -> visible (M,S,S) float coverage of mesh i where no other mesh is in front, full (M,S,S) its coverage with the other
+        meshes taken away, group_samples (M,2) int32 samples of each; device tensors"""
+        verts, faces = mesh_geometry(meshes, self.device)
+        out = renderer.render_instances(verts, faces, mesh_face_group(meshes, self.device), len(meshes))
+        return out["visible"][0], out["full"][0], out["group_samples"][0]
+
     def prepare_side_rend(self, meshes, maxd=1.5, colors=None):
         """tensors for setup_side_renderer: y flipped, scaled so that the bounding box measures `maxd`, centred at the
         vertex mean.  The caller's meshes are not modified.  -> faces, textures, vertices"""
@@ -243,6 +252,15 @@ def mesh_tensors(meshes, colors, device):
     faces = [torch.as_tensor(np.asarray(m.f).astype(np.int32)).to(device) for m, _ in pairs]
     all_faces, textures = get_faces_and_textures(verts, faces, colors_list=[c for _, c in pairs])
     return torch.cat(verts, dim=1), all_faces, textures
+
+
+def mesh_geometry(meshes, device):
+    """meshes with .v / .f -> vertices (1, sum V, 3) float32 and faces (1, sum F, 3) int32 that index them, mesh after mesh,
+    on `device`: `mesh_tensors` without the textures"""
+    verts = [torch.as_tensor(np.asarray(m.v), dtype=torch.float32).to(device) for m in meshes]
+    first = np.cumsum([0] + [len(v) for v in verts[:-1]])
+    faces = [torch.as_tensor(np.asarray(m.f).astype(np.int32)).to(device) + int(o) for m, o in zip(meshes, first)]
+    return torch.cat(verts)[None], torch.cat(faces)[None]
 
 
 def mesh_face_opacity(meshes, mesh_opacity, device, colors=None):

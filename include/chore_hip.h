@@ -470,7 +470,43 @@ int chore_scene_layers_fwd(chore_handle* h,
     float* rgb, float* depth, float* alpha, int* sample_id, void* workspace, chore_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Evaluation metrics, fp64  (replace recon/eval/chamfer_distance.py:10-52 = sklearn kd-tree nearest neighbours, and
+ * Instance masks and visibility of meshes, forward only  (replaces neural_renderer's mode='visibility':
+ * external/neural_renderer/neural_renderer/renderer.py:79-117, visibility.py:12-34 and the atomicMax on face_visibility of
+ * forward_face_index_map, cuda/rasterize_cuda_kernel.cu:200-205; and makes the masks BEHAVE ships per frame: the object as
+ * seen, the object alone, the person).  Which mesh owns a sample, and which meshes would cover it if the others were not there.
+ * tri (B,F,3,3) is chore_render_fwd's, both windings already in the list; face_group (B,F) int32 or NULL = every face in
+ * group 0; 1 <= G <= 8; ssaa 1 or 2; size * ssaa <= 4096.  Per sample of the size * ssaa grid:
+ *   1. candidates: every face that hits the sample under chore_render_fwd's hit rule (the aligned 16 x 16 tile box test of
+ *      chore_silhouette_fwd and the near / far test included).  A NaN zp is no candidate (it never wins in chore_render_fwd);
+ *   2. the winner f* is the candidate with the smallest zp, then the smallest index: bit-identical to chore_render_fwd's
+ *      sample_face_index;
+ *   3. g(f) = face_group[b,f].  A face whose group lies outside 0..G-1 is an occluder: it takes part in 1 and 2 and is
+ *      counted in face_samples, and it belongs to no group.  The value is tested on the device, the host reads no device value;
+ *   4. vis_g = 1 iff a winner exists and g(f*) == g;
+ *   5. full_g = 1 iff at least one candidate has group g, whatever lies in front of it.
+ * Outputs, each may be NULL: visible, full (B,G,size,size) fp32, resolved exactly as chore_render_fwd resolves alpha (the
+ * samples summed in the order s = sy * ssaa + sx, times 1 / ssaa^2; row r holds sample row block size-1-r), so the values are
+ * multiples of 1/4 or of 1 and exact; face_samples (B,F) int32: the number of samples face f wins; group_samples (B,G,2)
+ * int32: the number of samples with vis_g, and with full_g; sample_face_index (B,size*ssaa,size*ssaa) int32, rows NOT
+ * flipped, -1 = none.
+ * The launches are a clear kernel (no memset node), chore_render_fwd's setup kernel and one tile kernel over the same bins, all
+ * on `stream`.  The counts are integer sums
+ * (group_samples: reduced in the workgroup to one integer add per workgroup, group and kind; face_samples: equal winners among
+ * a lane's samples merged before the add); there are no float atomics, so every output is bit-equal from call to call and
+ * under graph replay.  The counters are zeroed inside the call on `stream`.
+ * workspace: chore_instances_workspace_bytes(B, F, G, size, ssaa) bytes, 256-byte aligned: the render workspace (0 = a shape
+ * chore_render_fwd refuses, or G outside 1..8).  It depends on the shapes only, nothing is allocated and no device value is
+ * read by the host, so the call can be captured into a graph.
+ * CHORE_EINVAL, before anything is launched: whatever chore_render_fwd refuses for these sizes, G outside 1..8, a NULL tri
+ * or workspace, all five outputs NULL.
+ * ------------------------------------------------------------------------------------------- */
+size_t chore_instances_workspace_bytes(int B, int F, int G, int size, int ssaa);
+int chore_instances_fwd(chore_handle* h, const float* tri, const int* face_group, int B, int F, int G, int size, int ssaa,
+                        float near_z, float far_z, float* visible, float* full, int* face_samples, int* group_samples,
+                        int* sample_face_index, void* workspace, chore_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Evaluation metrics, fp64 (replace recon/eval/chamfer_distance.py:10-52 = sklearn kd-tree nearest neighbours, and
  * recon/eval/pose_utils.py compute_transform :145-180 / compute_similarity_transform :103-143).
  *   chore_eval_chamfer   out[0] = mean_i min_j |x_i - y_j| (direction 'x_to_y'), out[1] = the other direction
  *                        ('y_to_x'); 'bi' = out[0] + out[1].  Euclidean distances (not squared).  x (Nx,3), y (Ny,3) fp64.
