@@ -5,7 +5,8 @@
 // visibility.py:12-34, the atomicMax on face_visibility in forward_face_index_map, cuda/rasterize_cuda_kernel.cu:200-205)
 // and makes the three masks BEHAVE ships per frame (the person, the object as seen, the object alone) from the meshes.
 // The rule is chore_instances_fwd's in include/chore_hip.h.  Organisation:
-//   * the setup kernel, the bins and the walk are render.hip's (render_common.h): one walk of a tile over its bin's list, the
+//   * the clear kernel (raster_store.h; the bin counters and the two count outputs = 0), the setup kernel (raster_common.h), the
+//     bins and the walk (render_common.h) are the family's: one walk of a tile over its bin's list, the
 //     callback sees every face that hits a sample.  Per sample the lane keeps the (zp, f) minimum with the winner's group, and
 //     an 8-bit mask of the groups met.  Three chore_render_fwd calls (all meshes, each mesh alone) would walk the same bins
 //     three times and shade every sample on top.
@@ -23,16 +24,6 @@ namespace {
 
 constexpr int INST_MAX_GROUPS = 8;
 
-// the bin counters and the two count outputs = 0, in one grid.  A kernel, not hipMemsetAsync: the call is recorded into hipGraphs,
-// where memset nodes replay unreliably (see splat.hip).  A NULL output has n = 0
-__global__ __launch_bounds__(256) void instances_clear_kernel(int* __restrict__ count, size_t ncount, int* __restrict__ face_samples,
-                                                              size_t nface, int* __restrict__ group_samples, size_t ngroup) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < ncount) count[i] = 0;
-    if (i < nface) face_samples[i] = 0;
-    if (i < ngroup) group_samples[i] = 0;
-}
-
 template <int SS>
 __global__ __launch_bounds__(256) void instances_tile_kernel(const TriSetup* __restrict__ ts, const int* __restrict__ count,
                                                              const int* __restrict__ list, const int* __restrict__ face_group,
@@ -43,7 +34,6 @@ __global__ __launch_bounds__(256) void instances_tile_kernel(const TriSetup* __r
     constexpr int NS = SS * SS;
     __shared__ RbShared sh;
     __shared__ int gsum[4][INST_MAX_GROUPS];               // per wave and group: visible | full << 16
-    const int S = size * SS;
     const int b = blockIdx.z;
     const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
     const int* grp = face_group ? face_group + (size_t)b * F : nullptr;
@@ -89,13 +79,7 @@ __global__ __launch_bounds__(256) void instances_tile_kernel(const TriSetup* __r
         for (int d = 32; d; d >>= 1) packed += __shfl_xor(packed, d);
         if (ln == 0) gsum[wv][g] = packed;
     }
-    if (inside && sample_face_index) {
-#pragma unroll
-        for (int sy = 0; sy < SS; ++sy)
-#pragma unroll
-            for (int sx = 0; sx < SS; ++sx)
-                sample_face_index[((size_t)b * S + (py * SS + sy)) * S + (px * SS + sx)] = best[sy * SS + sx];
-    }
+    if (inside && sample_face_index) raster_store_sample_ids<SS>(sample_face_index, b, px, py, size, best);
     __syncthreads();
     if (group_samples && (int)threadIdx.x < 2 * G) {
         const int g = threadIdx.x >> 1, kind = threadIdx.x & 1;
@@ -154,21 +138,17 @@ extern "C" int chore_instances_fwd(chore_handle* h, const float* tri, const int*
     hipStream_t s = (hipStream_t)stream;
     const int S = size * ssaa, nb = rb_bins(S);
     const RenderWs w = render_ws(workspace, B, F, S);
-    const int n = B * F;
-    const size_t ncount = (size_t)B * nb * nb, nface = face_samples ? (size_t)n : 0, ngroup = group_samples ? (size_t)B * G * 2 : 0;
+    // the bin counters and the two count outputs = 0 in one grid, no keys; a NULL output has n = 0
+    const size_t ncount = (size_t)B * nb * nb, nface = face_samples ? (size_t)B * F : 0, ngroup = group_samples ? (size_t)B * G * 2 : 0;
     const size_t nclear = ncount > nface ? (ncount > ngroup ? ncount : ngroup) : (nface > ngroup ? nface : ngroup);
-    hipLaunchKernelGGL(instances_clear_kernel, dim3((unsigned)((nclear + 255) / 256)), dim3(256), 0, s, w.count, ncount, face_samples,
-                       nface, group_samples, ngroup);
+    raster_clear(s, nclear, nullptr, 0, w.count, ncount, face_samples, nface, group_samples, ngroup);
     CHORE_LAUNCH_CHECK(h, s);
-    hipLaunchKernelGGL(render_setup_kernel, dim3((n + 255) / 256), dim3(256), 0, s, tri, B, F, S, w.ts, w.count, w.list);
+    raster_setup(s, tri, B, F, S, w.ts, w.count, w.list);
     CHORE_LAUNCH_CHECK(h, s);
-    const dim3 grid((size + RB_TW - 1) / RB_TW, (size + RB_TH - 1) / RB_TH, B);
-    if (ssaa == 2)
-        hipLaunchKernelGGL(instances_tile_kernel<2>, grid, dim3(256), 0, s, w.ts, w.count, w.list, face_group, F, G, size,
-                           near_z, far_z, visible, full, face_samples, group_samples, sample_face_index);
-    else
-        hipLaunchKernelGGL(instances_tile_kernel<1>, grid, dim3(256), 0, s, w.ts, w.count, w.list, face_group, F, G, size,
-                           near_z, far_z, visible, full, face_samples, group_samples, sample_face_index);
+    raster_dispatch_ssaa(ssaa, [&](auto ss) {
+        hipLaunchKernelGGL(instances_tile_kernel<decltype(ss)::value>, rb_tile_grid(size, B), dim3(256), 0, s, w.ts, w.count, w.list,
+                           face_group, F, G, size, near_z, far_z, visible, full, face_samples, group_samples, sample_face_index);
+    });
     CHORE_LAUNCH_CHECK(h, s);
     return CHORE_OK;
 }

@@ -1,9 +1,10 @@
 // raster_common.h -- what the silhouette rasteriser (silhouette.hip) and the colour / depth rasteriser (render.hip,
-// render_bwd.hip) share: the per-triangle setup and the per-sample hit rule of neural_renderer's forward_face_index_map
-// (external/neural_renderer/neural_renderer/cuda/rasterize_cuda_kernel.cu:24-215), and the edge walk of its
-// backward_pixel_map (:290-549).  All kernels evaluate these very expressions (explicit __fmul_rn, fixed association,
-// -ffp-contract=off), so the face that wins a sample is the same bit for bit in them, and so is the alpha term of the
-// pixel-map gradient.
+// render_bwd.hip, and through render_common.h scene.hip and instances.hip) share: the per-triangle setup and the per-sample
+// hit rule of neural_renderer's forward_face_index_map (external/neural_renderer/neural_renderer/cuda/rasterize_cuda_kernel.cu:
+// 24-215), and the edge walk of its backward_pixel_map (:290-549).  All kernels evaluate these very expressions (explicit
+// __fmul_rn, fixed association, -ffp-contract=off), so the face that wins a sample is the same bit for bit in them, and so is the
+// alpha term of the pixel-map gradient.  Also here, once for the family: the setup kernel with its launch (raster_setup_kernel,
+// raster_setup; binning or not) and the in-order compaction of a workgroup's flags (raster_compact).
 #pragma once
 #include "common.h"
 
@@ -48,6 +49,65 @@ __device__ __forceinline__ void tri_setup(TriSetup& t, int size) {
             t.y1 = (int)fminf(ceilf(ymax) + 1.f, S - 1.f);
         }
     }
+}
+
+constexpr int RB_BIN = 256;          // coarse bin edge in samples: at most 16 x 16 bins (size * ssaa <= 4096)
+__host__ __device__ inline int rb_bins(int S) { return (S + RB_BIN - 1) / RB_BIN; }
+
+// The one setup kernel of the family: thread = (image, triangle) -> its TriSetup for an S x S grid.  BIN: also append every
+// front-facing, in-view triangle to the lists of the coarse bins its box meets (count [B*nb*nb], zeroed by the caller; list
+// [B*nb*nb][F]).  Without BIN the two pointers are not read.
+template <bool BIN>
+__global__ __launch_bounds__(256) void raster_setup_kernel(const float* __restrict__ faces, int B, int F, int S,
+                                                           TriSetup* __restrict__ ts, int* __restrict__ count,
+                                                           int* __restrict__ list) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * F) return;
+    TriSetup t;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) t.f[k] = faces[(size_t)i * 9 + k];
+    tri_setup(t, S);
+    ts[i] = t;
+    if constexpr (BIN) {
+        // culled triangles have x0 > x1; a triangle outside the view ends up with an empty clamped box as well
+        if (t.x0 > t.x1 || t.y0 > t.y1) return;
+        const int b = i / F, fn = i - b * F;
+        const int nb = rb_bins(S);
+        // 0 <= x0 <= x1 <= S - 1 here, so every bin index is inside [0, nb)
+        for (int by = t.y0 / RB_BIN; by <= t.y1 / RB_BIN; ++by)
+            for (int bx = t.x0 / RB_BIN; bx <= t.x1 / RB_BIN; ++bx) {
+                const size_t bin = ((size_t)b * nb + by) * nb + bx;
+                const int slot = atomicAdd(&count[bin], 1);     // < F: a triangle enters a bin's list at most once
+                list[bin * F + slot] = fn;
+            }
+    }
+}
+// its launch on stream s; count == NULL: no binning (the silhouette and the render backward)
+inline void raster_setup(hipStream_t s, const float* tri, int B, int F, int S, TriSetup* ts, int* count = nullptr,
+                         int* list = nullptr) {
+    const dim3 grid((B * F + 255) / 256);
+    if (count) hipLaunchKernelGGL(raster_setup_kernel<true>, grid, dim3(256), 0, s, tri, B, F, S, ts, count, list);
+    else hipLaunchKernelGGL(raster_setup_kernel<false>, grid, dim3(256), 0, s, tri, B, F, S, ts, count, list);
+}
+
+// Compaction in thread order over a 256-thread workgroup (keeps the z-buffer order deterministic): ballots and a prefix over the
+// four waves (one thread walking the 256 flags was 2.4 us per chunk, most of the silhouette kernel).  Every thread calls it; the
+// values of the threads with `keep` go to out[0, n) and n is returned.  wcnt: int[4] of LDS; wv, ln: the caller's wave and lane
+// (threadIdx.x >> 6, & 63: the walk has them in registers already, and computing them here again costs its tile kernels two VGPRs).
+// Both barriers are inside: out and n are valid for every thread afterwards, and wcnt may be written again.
+__device__ __forceinline__ int raster_compact(bool keep, int value, int* out, int* wcnt, int wv, int ln) {
+    const unsigned long long mb = __ballot(keep);
+    if (ln == 0) wcnt[wv] = __popcll(mb);
+    __syncthreads();
+    {
+        int base = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) base += q < wv ? wcnt[q] : 0;
+        if (keep) out[base + __popcll(mb & ((1ull << ln) - 1ull))] = value;
+    }
+    const int nh = (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);
+    __syncthreads();
+    return nh;
 }
 
 // normalised coordinate of the centre of pixel i of `size` (evaluated in double, stored as float, like the reference)

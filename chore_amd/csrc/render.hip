@@ -20,7 +20,9 @@
 //     stay in registers; texels and light are fetched once per sample after the loop.
 //   * resolve in the same launch: the lane averages its samples (rgb, depth, alpha alike, like F.avg_pool2d), flips the
 //     row, and stores channel-first.  The super-sampled buffers never reach memory unless sample_face_index is asked for.
-// The setup kernel, the walk and the shading live in render_common.h, which scene.hip compiles too.
+// This file holds the tile kernel's shading loop and the entry point.  The setup kernel is raster_common.h's (raster_setup), the
+// walk and the shading live in render_common.h, the resolve and id stores and the ssaa dispatch in raster_store.h; scene.hip,
+// instances.hip and render_bwd.hip compile the same helpers.
 #include "render_common.h"
 
 namespace {
@@ -34,7 +36,6 @@ __global__ __launch_bounds__(256) void render_tile_kernel(const TriSetup* __rest
                                                           float* __restrict__ alpha_out, int* __restrict__ sample_face_index) {
     constexpr int NS = SS * SS;
     __shared__ RbShared sh;
-    const int S = size * SS;
     const int b = blockIdx.z;
     const TriSetup* tsb = ts + (size_t)b * F;
     int px, py;
@@ -56,20 +57,8 @@ __global__ __launch_bounds__(256) void render_tile_kernel(const TriSetup* __rest
         for (int k = 0; k < 3; ++k) acc[k] += c[k];
         zacc += zb[s];
     }
-    constexpr float inv_ns = 1.f / NS;
-    const int row = size - 1 - py;                        // rasterize_rgbad flips the rows
-    const size_t plane = (size_t)size * size, o = (size_t)row * size + px;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) rgb[((size_t)b * 3 + k) * plane + o] = acc[k] * inv_ns;
-    depth_out[(size_t)b * plane + o] = zacc * inv_ns;
-    alpha_out[(size_t)b * plane + o] = aacc * inv_ns;
-    if (sample_face_index) {
-#pragma unroll
-        for (int sy = 0; sy < SS; ++sy)
-#pragma unroll
-            for (int sx = 0; sx < SS; ++sx)
-                sample_face_index[((size_t)b * S + (py * SS + sy)) * S + (px * SS + sx)] = best[sy * SS + sx];
-    }
+    raster_store_resolved<NS>(b, px, py, size, acc, zacc, aacc, rgb, depth_out, alpha_out);
+    if (sample_face_index) raster_store_sample_ids<SS>(sample_face_index, b, px, py, size, best);
 }
 
 }  // namespace
@@ -92,18 +81,13 @@ extern "C" int chore_render_fwd(chore_handle* h, const float* tri, const float* 
     const int S = size * ssaa, nb = rb_bins(S);
     const RenderWs w = render_ws(workspace, B, F, S);
     CHORE_HIP_CHECK(h, hipMemsetAsync(w.count, 0, (size_t)B * nb * nb * sizeof(int), s));
-    const int n = B * F;
-    hipLaunchKernelGGL(render_setup_kernel, dim3((n + 255) / 256), dim3(256), 0, s, tri, B, F, S, w.ts, w.count, w.list);
+    raster_setup(s, tri, B, F, S, w.ts, w.count, w.list);
     CHORE_LAUNCH_CHECK(h, s);
-    const dim3 grid((size + RB_TW - 1) / RB_TW, (size + RB_TH - 1) / RB_TH, B);
-    if (ssaa == 2)
-        hipLaunchKernelGGL(render_tile_kernel<2>, grid, dim3(256), 0, s, w.ts, w.count, w.list, textures, light, F, ts, size,
-                           near_z, far_z, tex_eps, background3[0], background3[1], background3[2], rgb, depth, alpha,
-                           sample_face_index);
-    else
-        hipLaunchKernelGGL(render_tile_kernel<1>, grid, dim3(256), 0, s, w.ts, w.count, w.list, textures, light, F, ts, size,
-                           near_z, far_z, tex_eps, background3[0], background3[1], background3[2], rgb, depth, alpha,
-                           sample_face_index);
+    raster_dispatch_ssaa(ssaa, [&](auto ss) {
+        hipLaunchKernelGGL(render_tile_kernel<decltype(ss)::value>, rb_tile_grid(size, B), dim3(256), 0, s, w.ts, w.count, w.list,
+                           textures, light, F, ts, size, near_z, far_z, tex_eps, background3[0], background3[1], background3[2], rgb,
+                           depth, alpha, sample_face_index);
+    });
     CHORE_LAUNCH_CHECK(h, s);
     return CHORE_OK;
 }

@@ -48,17 +48,6 @@ inline size_t render_bwd_ws_bytes(int B, int F, int ts, int size, int ssaa) {
     return rb_align((size_t)B * F * sizeof(TriSetup)) + (size_t)B * S * S * (2 * sizeof(float4) + sizeof(float));
 }
 
-__global__ __launch_bounds__(256) void rbw_setup_kernel(const float* __restrict__ faces, int n /*B*F*/, int S,
-                                                        TriSetup* __restrict__ ts) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    TriSetup t;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) t.f[k] = faces[(size_t)i * 9 + k];
-    tri_setup(t, S);
-    ts[i] = t;
-}
-
 // thread = sample (x fastest): its colour and alpha as the forward produced them, and its share of the upstream gradients
 __global__ __launch_bounds__(256) void rbw_sample_kernel(const TriSetup* __restrict__ ts, const float* __restrict__ textures,
                                                          const float* __restrict__ light, const int* __restrict__ fim, int F,
@@ -191,29 +180,10 @@ __global__ __launch_bounds__(256) void rbw_gather_kernel(const TriSetup* __restr
                 const float g[3] = {g4.x, g4.y, g4.z};
                 float fr[3];
                 int ti[3];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {        // the forward's sampling position (rb_shade)
-                    float tif = (w[k] * (float)(tsz - 1)) * (zp / t.f[3 * k + 2]);
-                    tif = fminf(fmaxf(tif, 0.f), tmax);
-                    ti[k] = (int)tif;
-                    fr[k] = tif - (float)ti[k];
-                }
+                rb_tex_pos(t.f, w, zp, tsz, tmax, ti, fr);      // the forward's sampling position: rb_shade calls the same
                 if (pass == 0 && grad_light) {       // d light = d rgb x the blended texel
-                    float c[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int pn = 0; pn < 8; ++pn) {
-                        float wt = 1.f;
-                        int idx[3];
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) {
-                            const int up = (pn >> k) & 1;
-                            wt *= up ? fr[k] : 1.f - fr[k];
-                            idx[k] = min(ti[k] + up, tsz - 1);
-                        }
-                        const float* tq = tex + ((idx[0] * tsz + idx[1]) * tsz + idx[2]) * 3;
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) c[k] += wt * tq[k];
-                    }
+                    float c[3];
+                    rb_tex_blend(tex, tsz, ti, fr, c);
 #pragma unroll
                     for (int k = 0; k < 3; ++k) acc[3 + k] += g[k] * c[k];
                 }
@@ -305,7 +275,7 @@ extern "C" int chore_render_bwd(chore_handle* h, const float* tri, const float* 
         return CHORE_OK;
     }
     const RenderBwdWs w = render_bwd_ws(workspace, B, F, S);
-    hipLaunchKernelGGL(rbw_setup_kernel, dim3((n + 255) / 256), dim3(256), 0, s, tri, n, S, w.ts);
+    raster_setup(s, tri, B, F, S, w.ts);
     CHORE_LAUNCH_CHECK(h, s);
     hipLaunchKernelGGL(rbw_sample_kernel, dim3((S + 63) / 64, (S + 3) / 4, B), dim3(256), 0, s, w.ts, textures, light,
                        sample_face_index, F, ts, size, ssaa, tex_eps, background3[0], background3[1], background3[2], grad_rgb,

@@ -1,18 +1,18 @@
-// render_common.h -- what the colour / depth rasteriser (render.hip) and the scene rasteriser (scene.hip) share: the workspace
-// layout, the setup-and-binning kernel, the tile's walk over its bin list that leaves every sample's winning face in
-// registers, and the texture-and-light shading of a winner.  Both files compile these very expressions, so a sample's
-// face, depth and colour are the same bit for bit in both.  render.hip's head comment explains the organisation.
+// render_common.h -- what the binned triangle rasterisers (render.hip, render_bwd.hip, scene.hip, instances.hip) share: the
+// workspace layout, the tile grid, the tile's walk over its bin list that leaves every sample's winning face (or its K nearest)
+// in registers, and the texture-and-light shading of a winner with the texel rule the backward differentiates (rb_tex_pos,
+// rb_tex_blend).  All files compile these very expressions, so a sample's face, depth and colour are the same bit for bit in
+// them.  The setup-and-binning kernel is raster_common.h's, the resolve and id stores raster_store.h's.  render.hip's head
+// comment explains the organisation.
 #pragma once
 #include "raster_common.h"
+#include "raster_store.h"
 
 namespace {
 
-constexpr int RB_BIN = 256;          // coarse bin edge in samples: at most 16 x 16 bins (size * ssaa <= 4096)
 constexpr int RB_TW = 16, RB_TH = 16; // output pixels per tile; a wave owns an 8 x 8 quadrant
 constexpr int RB_CHUNK = 256;        // list entries looked at per pass
 constexpr int RB_TRI_WORDS = 22;     // f[9] + inv[9] + the box: a whole TriSetup
-
-__host__ __device__ inline int rb_bins(int S) { return (S + RB_BIN - 1) / RB_BIN; }
 
 // workspace: TriSetup [B*F] | counters int [B*nb*nb] | lists int [B*nb*nb][F]   (each part padded to 256 bytes)
 struct RenderWs {
@@ -44,28 +44,8 @@ inline bool render_shape_ok(int B, int F, int ts, int size, int ssaa) {
              (long long)B * F > 0x7fffffffLL / 32);
 }
 
-__global__ __launch_bounds__(256) void render_setup_kernel(const float* __restrict__ faces, int B, int F, int S,
-                                                           TriSetup* __restrict__ ts, int* __restrict__ count,
-                                                           int* __restrict__ list) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= B * F) return;
-    TriSetup t;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) t.f[k] = faces[(size_t)i * 9 + k];
-    tri_setup(t, S);
-    ts[i] = t;
-    // culled triangles have x0 > x1; a triangle outside the view ends up with an empty clamped box as well
-    if (t.x0 > t.x1 || t.y0 > t.y1) return;
-    const int b = i / F, fn = i - b * F;
-    const int nb = rb_bins(S);
-    // 0 <= x0 <= x1 <= S - 1 here, so every bin index is inside [0, nb)
-    for (int by = t.y0 / RB_BIN; by <= t.y1 / RB_BIN; ++by)
-        for (int bx = t.x0 / RB_BIN; bx <= t.x1 / RB_BIN; ++bx) {
-            const size_t bin = ((size_t)b * nb + by) * nb + bx;
-            const int slot = atomicAdd(&count[bin], 1);     // < F: a triangle enters a bin's list at most once
-            list[bin * F + slot] = fn;
-        }
-}
+// the tile kernels' grid: block x, y = tile of RB_TW x RB_TH output pixels, z = image
+inline dim3 rb_tile_grid(int size, int B) { return dim3((size + RB_TW - 1) / RB_TW, (size + RB_TH - 1) / RB_TH, B); }
 
 struct RbShared {                                      // a tile kernel's LDS
     int tri[RB_CHUNK][RB_TRI_WORDS];                   // 22 KB
@@ -115,17 +95,7 @@ __device__ __forceinline__ void rb_walk_hits(RbShared& sh, const TriSetup* __res
             const int x0 = t->x0, x1 = t->x1, y0 = t->y0, y1 = t->y1;
             meets = x0 <= sx1 && x1 >= sx0 && y0 <= sy1 && y1 >= sy0;
         }
-        const unsigned long long mb = __ballot(meets);
-        if (ln == 0) sh.wcnt[wv] = __popcll(mb);
-        __syncthreads();
-        {
-            int base = 0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) base += q < wv ? sh.wcnt[q] : 0;
-            if (meets) sh.hits[base + __popcll(mb & ((1ull << ln) - 1ull))] = fn;
-        }
-        const int nh = (sh.wcnt[0] + sh.wcnt[1]) + (sh.wcnt[2] + sh.wcnt[3]);
-        __syncthreads();
+        const int nh = raster_compact(meets, fn, sh.hits, sh.wcnt, wv, ln);
         static_assert(sizeof(TriSetup) == RB_TRI_WORDS * sizeof(int), "TriSetup is copied word by word");
         for (int e = threadIdx.x; e < nh * RB_TRI_WORDS; e += 256) {
             const int j = e / RB_TRI_WORDS, k = e - j * RB_TRI_WORDS;
@@ -227,22 +197,21 @@ __device__ __forceinline__ void rb_walk_layers(RbShared& sh, const TriSetup* __r
     });
 }
 
-// colour of face `face` of image b at weights w and depth z: the trilinear blend of its texture cube, times its light
-__device__ __forceinline__ void rb_shade(const TriSetup* __restrict__ tsb, const float* __restrict__ textures,
-                                         const float* __restrict__ light, int b, int F, int face, int tsz, float tex_eps,
-                                         const float* w3, float z, float* c) {
-    const float tmax = (float)(tsz - 1) - tex_eps;
-    const TriSetup* t = tsb + face;
-    const float* tex = textures + ((size_t)b * F + face) * tsz * tsz * tsz * 3;
-    float fr[3];
-    int ti[3];
+// The texel rule, once for the forward and the backward (the renderer's gradient is right only while both sample alike).
+// Where weights w3 at depth z sample the texture cube of the triangle with vertices f (x y z x y z x y z): the lower tap ti[k] and
+// the fraction fr[k] towards the upper one along each axis; tmax = (tsz - 1) - tex_eps.
+__device__ __forceinline__ void rb_tex_pos(const float* f, const float* w3, float z, int tsz, float tmax, int* ti, float* fr) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        float tif = (w3[k] * (float)(tsz - 1)) * (z / t->f[3 * k + 2]);
+        float tif = (w3[k] * (float)(tsz - 1)) * (z / f[3 * k + 2]);
         tif = fminf(fmaxf(tif, 0.f), tmax);
         ti[k] = (int)tif;
         fr[k] = tif - (float)ti[k];
     }
+}
+
+// the trilinear blend of the eight taps around (ti, fr) of one face's cube `tex` -> c[3]
+__device__ __forceinline__ void rb_tex_blend(const float* __restrict__ tex, int tsz, const int* ti, const float* fr, float* c) {
     c[0] = c[1] = c[2] = 0.f;
 #pragma unroll
     for (int pn = 0; pn < 8; ++pn) {
@@ -258,6 +227,16 @@ __device__ __forceinline__ void rb_shade(const TriSetup* __restrict__ tsb, const
 #pragma unroll
         for (int k = 0; k < 3; ++k) c[k] += w * q[k];
     }
+}
+
+// colour of face `face` of image b at weights w and depth z: the trilinear blend of its texture cube, times its light
+__device__ __forceinline__ void rb_shade(const TriSetup* __restrict__ tsb, const float* __restrict__ textures,
+                                         const float* __restrict__ light, int b, int F, int face, int tsz, float tex_eps,
+                                         const float* w3, float z, float* c) {
+    float fr[3];
+    int ti[3];
+    rb_tex_pos(tsb[face].f, w3, z, tsz, (float)(tsz - 1) - tex_eps, ti, fr);
+    rb_tex_blend(textures + ((size_t)b * F + face) * tsz * tsz * tsz * 3, tsz, ti, fr, c);
     if (light) {
         const float* l = light + ((size_t)b * F + face) * 3;
 #pragma unroll

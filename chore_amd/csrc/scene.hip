@@ -12,24 +12,43 @@
 //     behind it or the background.  chore_scene_layers_fwd keeps up to 8 faces per sample, optionally one per group of faces
 //     (a mesh), and composites them front to back over the point layer: scene_layers_tile_kernel, whose lists are
 //     rb_walk_layers' registers.  With one layer it launches scene_tile_kernel.
-//   * the call is a clear kernel (keys = empty, bin counters = 0; no hipMemsetAsync, whose byte-memset nodes replay
-//     unreliably in hipGraphs, see splat.hip), the setup kernel, the point pass and the tile kernel, all on the caller's
+//   * the call is the clear kernel (keys = empty, bin counters = 0; no hipMemsetAsync, whose byte-memset nodes replay
+//     unreliably in hipGraphs, see raster_store.h), the setup kernel, the point pass and the tile kernel, all on the caller's
 //     stream; nothing is allocated or read back, so it can be captured.
 //   * workspace: render.hip's workspace, padded to 256 bytes, then the keys.
+// This file holds the two tile kernels, what they alone share (scene_point_layer: key -> the point's colour, depth, alpha and
+// id; scene_over: the blend of a face over what is behind it) and the entry points; everything else is the common headers'.
 #include "render_common.h"
 #include "splat_common.h"
 
 namespace {
 
-// keys[0, nkeys) = SP_EMPTY (16-byte stores where a pair is whole) and count[0, ncount) = 0, in one grid
-__global__ __launch_bounds__(256) void scene_clear_kernel(unsigned long long* __restrict__ keys, size_t nkeys,
-                                                          int* __restrict__ count, size_t ncount) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (2 * i + 1 < nkeys)
-        reinterpret_cast<ulonglong2*>(keys)[i] = make_ulonglong2(SP_EMPTY, SP_EMPTY);
-    else if (2 * i < nkeys)
-        keys[2 * i] = SP_EMPTY;
-    if (i < ncount) count[i] = 0;
+// The point layer of sample s of output pixel (px, py) of image b from its key: false = no point.  Otherwise c becomes the
+// point's colour (what shows if it is in front, and under the faces if not), z its depth, a = 1 and id = -2 - n.
+template <int SS>
+__device__ __forceinline__ bool scene_point_layer(unsigned long long key, const float* __restrict__ pts,
+                                                  const float* __restrict__ colors, const float* __restrict__ radius,
+                                                  float radius_px, int N, int b, int px, int py, int s, float Sf, float ambient,
+                                                  float direct, float near, float far, float* c, float& z, float& a, int& id) {
+    if (key == SP_EMPTY) return false;
+    const unsigned n = (unsigned)key;
+    sp_shade(pts, colors, radius, radius_px, SS, Sf, near, far, (size_t)b * N + n, px * SS + (s % SS), py * SS + (s / SS), ambient,
+             direct, c, z);
+    a = 1.f;
+    id = -2 - (int)n;
+    return true;
+}
+
+// a face of colour m and opacity o in [0, 1] over what is behind it: c = o m + (1 - o) c, and m itself for an opaque face
+__device__ __forceinline__ void scene_over(float o, const float* m, float* c) {
+    if (o >= 1.f) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) c[q] = m[q];
+    } else {
+        const float u = __fsub_rn(1.f, o);
+#pragma unroll
+        for (int q = 0; q < 3; ++q) c[q] = __fadd_rn(__fmul_rn(o, m[q]), __fmul_rn(u, c[q]));
+    }
 }
 
 template <int SS>
@@ -65,28 +84,15 @@ __global__ __launch_bounds__(256) void scene_tile_kernel(const TriSetup* __restr
     for (int s = 0; s < NS; ++s) {
         float c[3] = {bg0, bg1, bg2}, z = far, a = 0.f;
         id[s] = -1;
-        const bool pt = k[s] != SP_EMPTY;
-        if (pt) {                       // `c` becomes the point's colour: what shows if it is in front, and under a face if not
-            const unsigned n = (unsigned)k[s];
-            sp_shade(pts, colors, radius, radius_px, SS, Sf, near, far, (size_t)b * N + n, px * SS + (s % SS),
-                     py * SS + (s / SS), ambient, direct, c, z);
-            a = 1.f;
-            id[s] = -2 - (int)n;
-        }
+        const bool pt = scene_point_layer<SS>(k[s], pts, colors, radius, radius_px, N, b, px, py, s, Sf, ambient, direct, near, far,
+                                              c, z, a, id[s]);
         // equality goes to the face
         if (best[s] >= 0 && !(pt && __fsub_rn(z, bias) < zb[s])) {
             float m[3];
             rb_shade(tsb, textures, light, b, F, best[s], tsz, tex_eps, wb[s], zb[s], m);
             float o = 1.f;
             if (face_opacity) o = fminf(fmaxf(face_opacity[(size_t)b * F + best[s]], 0.f), 1.f);     // NaN -> 0
-            if (o >= 1.f) {
-#pragma unroll
-                for (int q = 0; q < 3; ++q) c[q] = m[q];
-            } else {
-                const float u = __fsub_rn(1.f, o);
-#pragma unroll
-                for (int q = 0; q < 3; ++q) c[q] = __fadd_rn(__fmul_rn(o, m[q]), __fmul_rn(u, c[q]));
-            }
+            scene_over(o, m, c);
             z = zb[s];
             a = pt ? 1.f : o;
             id[s] = best[s];
@@ -96,18 +102,8 @@ __global__ __launch_bounds__(256) void scene_tile_kernel(const TriSetup* __restr
         zacc += z;
         aacc += a;
     }
-    constexpr float inv_ns = 1.f / NS;
-    const int row = size - 1 - py;                        // the flip of chore_render_fwd
-    const size_t plane = (size_t)size * size, o = (size_t)row * size + px;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) rgb[((size_t)b * 3 + q) * plane + o] = acc[q] * inv_ns;
-    depth_out[(size_t)b * plane + o] = zacc * inv_ns;
-    alpha_out[(size_t)b * plane + o] = aacc * inv_ns;
-    if (sample_id) {
-#pragma unroll
-        for (int s = 0; s < NS; ++s)
-            sample_id[((size_t)b * S + (py * SS + s / SS)) * S + (px * SS + s % SS)] = id[s];
-    }
+    raster_store_resolved<NS>(b, px, py, size, acc, zacc, aacc, rgb, depth_out, alpha_out);      // chore_render_fwd's resolve
+    if (sample_id) raster_store_sample_ids<SS>(sample_id, b, px, py, size, id);
 }
 
 // scene_tile_kernel with a list of up to `layers` <= K faces per sample, one per group, instead of the one winner
@@ -147,14 +143,8 @@ __global__ __launch_bounds__(256) void scene_layers_tile_kernel(
     for (int s = 0; s < NS; ++s) {
         float c[3] = {bg0, bg1, bg2}, z = far, a = 0.f;
         id[s] = -1;
-        const bool pt = k[s] != SP_EMPTY;
-        if (pt) {                       // `c` becomes the point's colour: what shows if it is in front, and under the faces if not
-            const unsigned n = (unsigned)k[s];
-            sp_shade(pts, colors, radius, radius_px, SS, Sf, near, far, (size_t)b * N + n, px * SS + (s % SS),
-                     py * SS + (s / SS), ambient, direct, c, z);
-            a = 1.f;
-            id[s] = -2 - (int)n;
-        }
+        const bool pt = scene_point_layer<SS>(k[s], pts, colors, radius, radius_px, N, b, px, py, s, Sf, ambient, direct, near, far,
+                                              c, z, a, id[s]);
         // j listed faces lie before the point (equality goes to the face); depths ascend, so they are the first j
         const float zt = __fsub_rn(z, bias);
         int j = 0;
@@ -187,15 +177,9 @@ __global__ __launch_bounds__(256) void scene_layers_tile_kernel(
                 float w[3], zr, m[3];
                 raster_weights(tf, tf + 9, (float)xi, (float)yi, w, zr);       // the walk's own expressions: zr == zi
                 rb_shade(tsb, textures, light, b, F, fi, tsz, tex_eps, w, zi, m);
-                const float o = opacity(fi), u = __fsub_rn(1.f, o);
-                if (o >= 1.f) {
-#pragma unroll
-                    for (int q = 0; q < 3; ++q) c[q] = m[q];
-                } else {
-#pragma unroll
-                    for (int q = 0; q < 3; ++q) c[q] = __fadd_rn(__fmul_rn(o, m[q]), __fmul_rn(u, c[q]));
-                }
-                al = __fadd_rn(o, __fmul_rn(u, al));
+                const float o = opacity(fi);
+                scene_over(o, m, c);
+                al = __fadd_rn(o, __fmul_rn(__fsub_rn(1.f, o), al));
             }
             z = lz[s][0];
             a = (pt || cut) ? 1.f : al;
@@ -206,18 +190,8 @@ __global__ __launch_bounds__(256) void scene_layers_tile_kernel(
         zacc += z;
         aacc += a;
     }
-    constexpr float inv_ns = 1.f / NS;
-    const int row = size - 1 - py;                        // the flip of chore_render_fwd
-    const size_t plane = (size_t)size * size, o = (size_t)row * size + px;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) rgb[((size_t)b * 3 + q) * plane + o] = acc[q] * inv_ns;
-    depth_out[(size_t)b * plane + o] = zacc * inv_ns;
-    alpha_out[(size_t)b * plane + o] = aacc * inv_ns;
-    if (sample_id) {
-#pragma unroll
-        for (int s = 0; s < NS; ++s)
-            sample_id[((size_t)b * S + (py * SS + s / SS)) * S + (px * SS + s % SS)] = id[s];
-    }
+    raster_store_resolved<NS>(b, px, py, size, acc, zacc, aacc, rgb, depth_out, alpha_out);      // chore_render_fwd's resolve
+    if (sample_id) raster_store_sample_ids<SS>(sample_id, b, px, py, size, id);
 }
 
 }  // namespace
@@ -241,42 +215,36 @@ static int scene_fwd(chore_handle* h, const char* who, const float* tri, const f
     if (ssaa != 1 && ssaa != 2) CHORE_FAIL(h, CHORE_EINVAL, "%s: ssaa must be 1 or 2, got %d", who, ssaa);
     if (!render_shape_ok(B, F, ts, size, ssaa) || !splat_shape_ok(B, N, size, ssaa))
         CHORE_FAIL(h, CHORE_EINVAL, "%s: bad sizes B=%d F=%d ts=%d N=%d size=%d ssaa=%d", who, B, F, ts, N, size, ssaa);
-    if (!(ambient >= 0.f && ambient <= 1.f))
-        CHORE_FAIL(h, CHORE_EINVAL, "%s: ambient must lie in [0, 1], got %g", who, (double)ambient);
-    if (!(near_z < far_z))
-        CHORE_FAIL(h, CHORE_EINVAL, "%s: near_z %g must be below far_z %g", who, (double)near_z, (double)far_z);
-    if (!radius && !(radius_px > 0.f))
-        CHORE_FAIL(h, CHORE_EINVAL, "%s: radius_px must be positive without per-point radii, got %g", who, (double)radius_px);
+    if (int rc = sp_check_args(h, who, ambient, near_z, far_z, radius, radius_px)) return rc;
     if (!(point_depth_bias >= 0.f))
         CHORE_FAIL(h, CHORE_EINVAL, "%s: point_depth_bias must be >= 0, got %g", who, (double)point_depth_bias);
     hipStream_t s = (hipStream_t)stream;
-    const int S = size * ssaa, nb = rb_bins(S), total = B * N, nf = B * F;
+    const int S = size * ssaa, nb = rb_bins(S);
     const RenderWs w = render_ws(workspace, B, F, S);
     unsigned long long* keys = (unsigned long long*)((char*)workspace + rb_align(render_ws_bytes(B, F, size, ssaa)));
     const size_t nkeys = (size_t)B * S * S, ncount = (size_t)B * nb * nb;
-    const size_t nclear = (nkeys + 1) / 2 > ncount ? (nkeys + 1) / 2 : ncount;  // a thread clears two keys and one counter
-    hipLaunchKernelGGL(scene_clear_kernel, dim3((unsigned)((nclear + 255) / 256)), dim3(256), 0, s, keys, nkeys, w.count, ncount);
+    raster_clear(s, (nkeys + 1) / 2 > ncount ? (nkeys + 1) / 2 : ncount, keys, nkeys, w.count, ncount);
     CHORE_LAUNCH_CHECK(h, s);
-    hipLaunchKernelGGL(render_setup_kernel, dim3((nf + 255) / 256), dim3(256), 0, s, tri, B, F, S, w.ts, w.count, w.list);
+    raster_setup(s, tri, B, F, S, w.ts, w.count, w.list);
     CHORE_LAUNCH_CHECK(h, s);
-    hipLaunchKernelGGL(splat_kernel, dim3((total + SP_BLOCK - 1) / SP_BLOCK), dim3(SP_BLOCK), 0, s, pts, radius, radius_px, total, N, S,
-                       ssaa, near_z, far_z, keys);
+    splat_pass(s, pts, radius, radius_px, B, N, S, ssaa, near_z, far_z, keys);
     CHORE_LAUNCH_CHECK(h, s);
-    const dim3 grid((size + RB_TW - 1) / RB_TW, (size + RB_TH - 1) / RB_TH, B);
-    if (layers == 1) {
-        const auto kernel = ssaa == 2 ? scene_tile_kernel<2> : scene_tile_kernel<1>;
-        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, w.ts, w.count, w.list, textures, light, face_opacity, F, ts, keys, pts,
-                           point_rgb, radius, radius_px, N, point_depth_bias, size, ambient, near_z, far_z, tex_eps, background3[0],
-                           background3[1], background3[2], rgb, depth, alpha, sample_id);
-    } else {
-        // capacities 2, 4 and 8; a request between two of them runs in the larger with its list cut at `layers`
-        const auto kernel = layers <= 2 ? (ssaa == 2 ? scene_layers_tile_kernel<2, 2> : scene_layers_tile_kernel<1, 2>)
-                          : layers <= 4 ? (ssaa == 2 ? scene_layers_tile_kernel<2, 4> : scene_layers_tile_kernel<1, 4>)
-                                        : (ssaa == 2 ? scene_layers_tile_kernel<2, 8> : scene_layers_tile_kernel<1, 8>);
-        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, w.ts, w.count, w.list, textures, light, face_opacity, face_group, layers, F,
-                           ts, keys, pts, point_rgb, radius, radius_px, N, point_depth_bias, size, ambient, near_z, far_z, tex_eps,
-                           background3[0], background3[1], background3[2], rgb, depth, alpha, sample_id);
-    }
+    raster_dispatch_ssaa(ssaa, [&](auto ss) {
+        constexpr int SS = decltype(ss)::value;
+        const dim3 grid = rb_tile_grid(size, B);
+        if (layers == 1) {
+            hipLaunchKernelGGL(scene_tile_kernel<SS>, grid, dim3(256), 0, s, w.ts, w.count, w.list, textures, light, face_opacity, F, ts,
+                               keys, pts, point_rgb, radius, radius_px, N, point_depth_bias, size, ambient, near_z, far_z, tex_eps,
+                               background3[0], background3[1], background3[2], rgb, depth, alpha, sample_id);
+        } else {
+            // capacities 2, 4 and 8; a request between two of them runs in the larger with its list cut at `layers`
+            const auto kernel = layers <= 2 ? scene_layers_tile_kernel<SS, 2>
+                              : layers <= 4 ? scene_layers_tile_kernel<SS, 4> : scene_layers_tile_kernel<SS, 8>;
+            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, w.ts, w.count, w.list, textures, light, face_opacity, face_group, layers,
+                               F, ts, keys, pts, point_rgb, radius, radius_px, N, point_depth_bias, size, ambient, near_z, far_z,
+                               tex_eps, background3[0], background3[1], background3[2], rgb, depth, alpha, sample_id);
+        }
+    });
     CHORE_LAUNCH_CHECK(h, s);
     return CHORE_OK;
 }

@@ -19,19 +19,9 @@
 //     in flight; the per-vertex sums are combined by a fixed butterfly, so the result is deterministic.
 // Degenerate edges (a zero denominator makes the crossing coordinate non-finite) are skipped, like the
 // restatement in oracle/silhouette.py does; with real-valued vertices they have measure zero.
-#include "raster_common.h"     // TriSetup, tri_backside, tri_setup, raster_hit: shared with render.hip
+#include "raster_common.h"     // TriSetup, the setup kernel, raster_hit, raster_compact, the edge walk: shared with render.hip
 
 namespace {
-
-__global__ void sil_setup_kernel(const float* __restrict__ faces, int n /*B*F*/, int size, TriSetup* __restrict__ ts) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    TriSetup t;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) t.f[k] = faces[(size_t)i * 9 + k];
-    tri_setup(t, size);
-    ts[i] = t;
-}
 
 constexpr int TILE_PX = 16, CHUNK = 256;
 
@@ -58,20 +48,8 @@ __global__ __launch_bounds__(256) void sil_fwd_kernel(const TriSetup* __restrict
             meets = t.x0 <= t.x1 && t.x0 <= tx0 + TILE_PX - 1 && t.x1 >= tx0 && t.y0 <= ty0 + TILE_PX - 1 && t.y1 >= ty0;
             tri[threadIdx.x] = t;
         }
-        // compact in index order (keeps the z-buffer order deterministic): ballots and a prefix over the four waves (one
-        // thread walking the 256 flags was 2.4 us per chunk, most of the kernel)
-        const unsigned long long mb = __ballot(meets);
-        const int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
-        if (ln == 0) wcnt[wv] = __popcll(mb);
-        __syncthreads();
-        {
-            int base = 0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) base += q < wv ? wcnt[q] : 0;
-            if (meets) hits[base + __popcll(mb & ((1ull << ln) - 1ull))] = threadIdx.x;
-        }
-        const int nh = (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);
-        __syncthreads();
+        // in index order: a deterministic z-buffer order
+        const int nh = raster_compact(meets, threadIdx.x, hits, wcnt, threadIdx.x >> 6, threadIdx.x & 63);
         if (inside) {
             for (int h = 0; h < nh; ++h) {
                 const int j = hits[h];
@@ -259,8 +237,7 @@ extern "C" int chore_silhouette_fwd(chore_handle* h, const float* faces, int B, 
         CHORE_FAIL(h, CHORE_EINVAL, "chore_silhouette_fwd: bad sizes B=%d F=%d size=%d", B, F, size);
     hipStream_t s = (hipStream_t)stream;
     TriSetup* ts = (TriSetup*)workspace;
-    const int n = B * F;
-    hipLaunchKernelGGL(sil_setup_kernel, dim3((n + 255) / 256), dim3(256), 0, s, faces, n, size, ts);
+    raster_setup(s, faces, B, F, size, ts);
     const int tiles = (size + TILE_PX - 1) / TILE_PX;
     hipLaunchKernelGGL(sil_fwd_kernel, dim3(tiles, tiles, B), dim3(256), 0, s, ts, F, size, near_z, far_z, face_index,
                        alpha);

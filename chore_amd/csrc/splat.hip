@@ -16,20 +16,12 @@
 //     each winner with the very expressions of the coverage test, shades, averages, flips the row, stores channel-first.
 // Every expression that decides coverage is spelled with __fmul_rn / __fadd_rn / __fsub_rn in a fixed association (and the
 // library is built with -ffp-contract=off), so tests/splat_ref.py reproduces the winners in numpy float32.
-// The point helpers, splat_kernel, the key loads and the disc shading live in splat_common.h, which scene.hip compiles too.
+// This file holds the resolve kernel and the entry point.  The point helpers, splat_kernel with its launch, the key loads, the
+// disc shading and the argument checks live in splat_common.h, which scene.hip compiles too; the clear kernel (keys = empty; why
+// it is a kernel is said there), the resolve and id stores and the ssaa dispatch in raster_store.h.
 #include "splat_common.h"
 
 namespace {
-
-// every key = SP_EMPTY.  A kernel, not hipMemsetAsync: the call is recorded into hipGraphs, where byte-memset nodes replay
-// unreliably (GPU memory faults; contact.hip fills its workspace with a kernel for the same reason).  16-byte stores; n keys.
-__global__ __launch_bounds__(256) void splat_clear_kernel(unsigned long long* __restrict__ keys, size_t n) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (2 * i + 1 < n)
-        reinterpret_cast<ulonglong2*>(keys)[i] = make_ulonglong2(SP_EMPTY, SP_EMPTY);
-    else if (2 * i < n)
-        keys[2 * i] = SP_EMPTY;
-}
 
 template <int SS>
 __global__ __launch_bounds__(256) void splat_resolve_kernel(const unsigned long long* __restrict__ keys,
@@ -50,9 +42,11 @@ __global__ __launch_bounds__(256) void splat_resolve_kernel(const unsigned long 
     unsigned long long k[NS];
     sp_load_keys<SS>(kb, S, px, py, k);
     float acc[3] = {0.f, 0.f, 0.f}, zacc = 0.f, aacc = 0.f;
+    int id[NS];
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
         float c[3] = {bg0, bg1, bg2}, z = far;
+        id[s] = k[s] == SP_EMPTY ? -1 : (int)(unsigned)k[s];
         if (k[s] != SP_EMPTY) {
             const size_t i = (size_t)b * N + (unsigned)k[s];
             sp_shade(pts, colors, radius, radius_px, SS, Sf, near, far, i, px * SS + (s % SS), py * SS + (s / SS), ambient, direct, c, z);
@@ -62,19 +56,8 @@ __global__ __launch_bounds__(256) void splat_resolve_kernel(const unsigned long 
         for (int q = 0; q < 3; ++q) acc[q] += c[q];
         zacc += z;
     }
-    constexpr float inv_ns = 1.f / NS;
-    const int row = size - 1 - py;                        // the flip of chore_render_fwd
-    const size_t plane = (size_t)size * size, o = (size_t)row * size + px;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) rgb[((size_t)b * 3 + q) * plane + o] = acc[q] * inv_ns;
-    depth_out[(size_t)b * plane + o] = zacc * inv_ns;
-    alpha_out[(size_t)b * plane + o] = aacc * inv_ns;
-    if (sample_point_index) {
-#pragma unroll
-        for (int s = 0; s < NS; ++s)
-            sample_point_index[((size_t)b * S + (py * SS + s / SS)) * S + (px * SS + s % SS)] =
-                k[s] == SP_EMPTY ? -1 : (int)(unsigned)k[s];
-    }
+    raster_store_resolved<NS>(b, px, py, size, acc, zacc, aacc, rgb, depth_out, alpha_out);      // chore_render_fwd's resolve
+    if (sample_point_index) raster_store_sample_ids<SS>(sample_point_index, b, px, py, size, id);
 }
 
 }  // namespace
@@ -94,31 +77,20 @@ extern "C" int chore_splat_fwd(chore_handle* h, const float* pts, const float* r
     if (ssaa != 1 && ssaa != 2) CHORE_FAIL(h, CHORE_EINVAL, "chore_splat_fwd: ssaa must be 1 or 2, got %d", ssaa);
     if (!splat_shape_ok(B, N, size, ssaa))
         CHORE_FAIL(h, CHORE_EINVAL, "chore_splat_fwd: bad sizes B=%d N=%d size=%d ssaa=%d", B, N, size, ssaa);
-    if (!(ambient >= 0.f && ambient <= 1.f))
-        CHORE_FAIL(h, CHORE_EINVAL, "chore_splat_fwd: ambient must lie in [0, 1], got %g", (double)ambient);
-    if (!(near_z < far_z))
-        CHORE_FAIL(h, CHORE_EINVAL, "chore_splat_fwd: near_z %g must be below far_z %g", (double)near_z, (double)far_z);
-    if (!radius && !(radius_px > 0.f))
-        CHORE_FAIL(h, CHORE_EINVAL, "chore_splat_fwd: radius_px must be positive without per-point radii, got %g",
-                   (double)radius_px);
+    if (int rc = sp_check_args(h, "chore_splat_fwd", ambient, near_z, far_z, radius, radius_px)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const int S = size * ssaa, total = B * N;
+    const int S = size * ssaa;
     unsigned long long* keys = (unsigned long long*)workspace;
     const size_t nkeys = (size_t)B * S * S;
-    hipLaunchKernelGGL(splat_clear_kernel, dim3((unsigned)((nkeys / 2 + 256) / 256)), dim3(256), 0, s, keys, nkeys);
+    raster_clear(s, nkeys / 2 + 1, keys, nkeys);
     CHORE_LAUNCH_CHECK(h, s);
-    hipLaunchKernelGGL(splat_kernel, dim3((total + SP_BLOCK - 1) / SP_BLOCK), dim3(SP_BLOCK), 0, s, pts, radius, radius_px, total, N, S, ssaa,
-                       near_z, far_z, keys);
+    splat_pass(s, pts, radius, radius_px, B, N, S, ssaa, near_z, far_z, keys);
     CHORE_LAUNCH_CHECK(h, s);
-    const dim3 grid((size + 63) / 64, (size + 3) / 4, B);
-    if (ssaa == 2)
-        hipLaunchKernelGGL(splat_resolve_kernel<2>, grid, dim3(256), 0, s, keys, pts, rgb_in, radius, radius_px, N, size,
-                           ambient, near_z, far_z, background3[0], background3[1], background3[2], rgb, depth, alpha,
-                           sample_point_index);
-    else
-        hipLaunchKernelGGL(splat_resolve_kernel<1>, grid, dim3(256), 0, s, keys, pts, rgb_in, radius, radius_px, N, size,
-                           ambient, near_z, far_z, background3[0], background3[1], background3[2], rgb, depth, alpha,
-                           sample_point_index);
+    raster_dispatch_ssaa(ssaa, [&](auto ss) {
+        hipLaunchKernelGGL(splat_resolve_kernel<decltype(ss)::value>, dim3((size + 63) / 64, (size + 3) / 4, B), dim3(256), 0, s, keys,
+                           pts, rgb_in, radius, radius_px, N, size, ambient, near_z, far_z, background3[0], background3[1],
+                           background3[2], rgb, depth, alpha, sample_point_index);
+    });
     CHORE_LAUNCH_CHECK(h, s);
     return CHORE_OK;
 }

@@ -1,15 +1,15 @@
 // splat_common.h -- what the point rasteriser (splat.hip) and the scene rasteriser (scene.hip) share: the point helpers, the
-// point pass that fills the 64-bit sample keys, and the disc shading of a sample's winner.  Both files compile these very
+// point pass that fills the 64-bit sample keys with its launch, the disc shading of a sample's winner, and the checks of the
+// point arguments under the caller's name.  Both files compile these very
 // expressions (explicit __fmul_rn / __fadd_rn / __fsub_rn, fixed association, -ffp-contract=off), so the point that wins a
 // sample and its shaded colour are the same bit for bit in both.
 #pragma once
-#include "common.h"
+#include "raster_store.h"     // SP_EMPTY, the clear kernel, the resolve and id stores
 
 namespace {
 
 constexpr float SP_MAX_RS = 64.f;    // radii are clamped to this many samples
 constexpr float SP_LANE_RS = 2.f;    // up to here a disc is drawn by the lane that loaded it
-constexpr unsigned long long SP_EMPTY = ~0ull;
 
 // sample-space position of a normalised coordinate: raster_common.h's vertex expression, 0.5f * ((u * S + S) - 1.0f)
 __device__ __forceinline__ float sp_pos(float u, float Sf) {
@@ -143,6 +143,24 @@ inline bool splat_shape_ok(int B, int N, int size, int ssaa) {
 inline size_t splat_key_bytes(int B, int size, int ssaa) {
     const size_t S = (size_t)size * ssaa;
     return (size_t)B * S * S * sizeof(unsigned long long);
+}
+// the checks of the point arguments that chore_splat_fwd and the scene entry points share, under the caller's name
+inline int sp_check_args(chore_handle* h, const char* who, float ambient, float near_z, float far_z, const float* radius,
+                         float radius_px) {
+    if (!(ambient >= 0.f && ambient <= 1.f))
+        CHORE_FAIL(h, CHORE_EINVAL, "%s: ambient must lie in [0, 1], got %g", who, (double)ambient);
+    if (!(near_z < far_z))
+        CHORE_FAIL(h, CHORE_EINVAL, "%s: near_z %g must be below far_z %g", who, (double)near_z, (double)far_z);
+    if (!radius && !(radius_px > 0.f))
+        CHORE_FAIL(h, CHORE_EINVAL, "%s: radius_px must be positive without per-point radii, got %g", who, (double)radius_px);
+    return CHORE_OK;
+}
+// the point pass on stream s: every sample key of the (B, S, S) grid, cleared before, takes its nearest point
+inline void splat_pass(hipStream_t s, const float* pts, const float* radius, float radius_px, int B, int N, int S, int ssaa,
+                       float near_z, float far_z, unsigned long long* keys) {
+    const int total = B * N;
+    hipLaunchKernelGGL(splat_kernel, dim3((total + SP_BLOCK - 1) / SP_BLOCK), dim3(SP_BLOCK), 0, s, pts, radius, radius_px, total, N, S,
+                       ssaa, near_z, far_z, keys);
 }
 
 }  // namespace

@@ -51,30 +51,27 @@ def _vec(x, device, batch):
     return t[None, :].repeat(batch, 1) if t.dim() == 1 else t
 
 
-def look_at(vertices, eye, at=(0, 0, 0), up=(0, 1, 0)):
-    """look_at.py:6-62: camera at `eye` looking at `at`"""
+def _camera(vertices, eye, target, up, target_is_point):
+    """the vertices in the camera at `eye` that looks at the point `target`, or along the direction `target`"""
     if vertices.dim() != 3:
         raise ValueError("vertices Tensor should have 3 dimensions")
     B, dev = vertices.shape[0], vertices.device
-    eye, at, up = _vec(eye, dev, B), _vec(at, dev, B), _vec(up, dev, B)
-    z_axis = F.normalize(at - eye, eps=1e-5)
+    eye, target, up = _vec(eye, dev, B), _vec(target, dev, B), _vec(up, dev, B)
+    z_axis = F.normalize(target - eye if target_is_point else target, eps=1e-5)
     x_axis = F.normalize(torch.cross(up, z_axis, dim=1), eps=1e-5)
     y_axis = F.normalize(torch.cross(z_axis, x_axis, dim=1), eps=1e-5)
     r = torch.stack((x_axis, y_axis, z_axis), dim=1)
     return torch.matmul(vertices - eye[:, None, :], r.transpose(1, 2))
+
+
+def look_at(vertices, eye, at=(0, 0, 0), up=(0, 1, 0)):
+    """look_at.py:6-62: camera at `eye` looking at `at`"""
+    return _camera(vertices, eye, at, up, True)
 
 
 def look(vertices, eye, direction=(0, 1, 0), up=(0, 1, 0)):
     """look.py:6-55: camera at `eye` looking along `direction` (each (3,) or (B,3); the reference's default `up` is [0, 1, 0])"""
-    if vertices.dim() != 3:
-        raise ValueError("vertices Tensor should have 3 dimensions")
-    B, dev = vertices.shape[0], vertices.device
-    eye, direction, up = _vec(eye, dev, B), _vec(direction, dev, B), _vec(up, dev, B)
-    z_axis = F.normalize(direction, eps=1e-5)
-    x_axis = F.normalize(torch.cross(up, z_axis, dim=1), eps=1e-5)
-    y_axis = F.normalize(torch.cross(z_axis, x_axis, dim=1), eps=1e-5)
-    r = torch.stack((x_axis, y_axis, z_axis), dim=1)
-    return torch.matmul(vertices - eye[:, None, :], r.transpose(1, 2))
+    return _camera(vertices, eye, direction, up, False)
 
 
 def perspective(vertices, angle=30.):
@@ -115,6 +112,60 @@ def lighting(faces, textures, intensity_ambient=0.5, intensity_directional=0.5, 
     return textures * light[:, :, None, None, None, :]
 
 
+# ---- what every call into the library's rasterisers needs around it
+
+def _ptr(x):
+    return x.data_ptr() if x is not None else None
+
+
+def _stream(dev):
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def _background(background_color):
+    return (ctypes.c_float * 3)(*[float(c) for c in background_color])
+
+
+def _workspace(dev, query, what, **dims):
+    """the workspace of one call, query(*dims) bytes on `dev` (None: only the check); 0 bytes = a shape the library does not take"""
+    if query(*dims.values()) == 0:
+        raise ValueError("unsupported %s shape %s" % (what, " ".join("%s=%d" % kv for kv in dims.items())))
+    return None if dev is None else torch.empty(query(*dims.values()), dtype=torch.uint8, device=dev)
+
+
+def _outputs(dev, B, S, ssaa, index):
+    """rgb (B,3,S,S), depth (B,S,S), alpha (B,S,S) and, if asked for, the (B,S*ssaa,S*ssaa) int32 sample index (else None)"""
+    return (torch.empty(B, 3, S, S, dtype=torch.float32, device=dev), torch.empty(B, S, S, dtype=torch.float32, device=dev),
+            torch.empty(B, S, S, dtype=torch.float32, device=dev),
+            torch.empty(B, S * ssaa, S * ssaa, dtype=torch.int32, device=dev) if index else None)
+
+
+def _opt(x, dev, shape, what, shown=None):
+    """an optional tensor, detached, fp32 and contiguous on `dev`, of `shape` (named `shown` in the error); None stays None"""
+    if x is None:
+        return None
+    x = x.detach().to(dev).float().contiguous()
+    if tuple(x.shape) != shape:
+        raise ValueError("%s %s expected, got %s" % (what, shown or shape, tuple(x.shape)))
+    return x
+
+
+def _face_group(face_group, dev, B, Fn):
+    """(B,F) integer group ids as int32 on `dev`, or None"""
+    if face_group is None:
+        return None
+    if torch.is_floating_point(face_group) or tuple(face_group.shape) != (B, Fn):
+        raise ValueError("face_group: integers %s expected, got %s %s" % ((B, Fn), face_group.dtype, tuple(face_group.shape)))
+    return face_group.detach().to(dev).to(torch.int32).contiguous()
+
+
+def _radius(radius, dev, B, N, shown=None):
+    """a number or (B,N) radii -> (the per-point radii or None, the one radius or 0.0)"""
+    if torch.is_tensor(radius) and radius.dim() > 0:
+        return _opt(radius, dev, (B, N), "radius: a number or", shown), 0.0
+    return None, float(radius)
+
+
 class _RasterizeRGBAD(torch.autograd.Function):
     """chore_render_fwd / chore_render_bwd: (tri, textures, light or None) -> rgb, depth, alpha, sample_face_index.  The
     forward is the plain call with the sample index kept; an output that receives no gradient hands NULL to the backward,
@@ -138,20 +189,15 @@ class _RasterizeRGBAD(torch.autograd.Function):
         dev = tri.device
         h = _lib.handle(dev.index or 0)
         B, Fn, ts = tri.shape[0], tri.shape[1], tex.shape[2]
-        nbytes = _lib.lib.chore_render_bwd_workspace_bytes(B, Fn, ts, S, ssaa)
-        if nbytes == 0:
-            raise ValueError("unsupported render shape B=%d F=%d ts=%d image_size=%d ssaa=%d" % (B, Fn, ts, S, ssaa))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = _workspace(dev, _lib.lib.chore_render_bwd_workspace_bytes, "render", B=B, F=Fn, ts=ts, image_size=S, ssaa=ssaa)
         up = [g.float().contiguous() if g is not None else None for g in (g_rgb, g_depth, g_alpha)]
         g_tri = torch.empty_like(tri)
         g_tex = torch.empty_like(tex) if ctx.needs_input_grad[1] else None
         g_light = torch.empty_like(light) if light is not None and ctx.needs_input_grad[2] else None
-        ptr = lambda x: x.data_ptr() if x is not None else None      # noqa: E731
-        bg = (ctypes.c_float * 3)(*background)
-        _lib.check(_lib.lib.chore_render_bwd(h, tri.data_ptr(), tex.data_ptr(), ptr(light), fim.data_ptr(), B, Fn, ts, S, ssaa,
-                                             float(near), float(far), float(eps), float(eps), bg, ptr(up[0]), ptr(up[1]),
-                                             ptr(up[2]), g_tri.data_ptr(), ptr(g_tex), ptr(g_light), ws.data_ptr(),
-                                             torch.cuda.current_stream(dev).cuda_stream), h, "chore_render_bwd")
+        _lib.check(_lib.lib.chore_render_bwd(h, tri.data_ptr(), tex.data_ptr(), _ptr(light), fim.data_ptr(), B, Fn, ts, S, ssaa,
+                                             float(near), float(far), float(eps), float(eps), _background(background),
+                                             _ptr(up[0]), _ptr(up[1]), _ptr(up[2]), g_tri.data_ptr(), _ptr(g_tex), _ptr(g_light),
+                                             ws.data_ptr(), _stream(dev)), h, "chore_render_bwd")
         return g_tri, g_tex, g_light, None, None, None, None, None, None
 
 
@@ -160,20 +206,11 @@ def _render_fwd(tri, tex, lt, S, ssaa, near, far, eps, background_color, return_
     dev = tri.device
     h = _lib.handle(dev.index or 0)
     B, Fn = tri.shape[:2]
-    ts = tex.shape[2]
-    nbytes = _lib.lib.chore_render_workspace_bytes(B, Fn, S, ssaa)
-    if nbytes == 0:
-        raise ValueError("unsupported render shape B=%d F=%d image_size=%d ssaa=%d" % (B, Fn, S, ssaa))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    rgb = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
-    depth = torch.empty(B, S, S, dtype=torch.float32, device=dev)
-    alpha = torch.empty(B, S, S, dtype=torch.float32, device=dev)
-    fim = torch.empty(B, S * ssaa, S * ssaa, dtype=torch.int32, device=dev) if return_index else None
-    bg = (ctypes.c_float * 3)(*[float(c) for c in background_color])
-    _lib.check(_lib.lib.chore_render_fwd(h, tri.data_ptr(), tex.data_ptr(), lt.data_ptr() if lt is not None else None, B, Fn, ts,
-                                         S, ssaa, float(near), float(far), float(eps), bg, rgb.data_ptr(), depth.data_ptr(),
-                                         alpha.data_ptr(), fim.data_ptr() if return_index else None, ws.data_ptr(),
-                                         torch.cuda.current_stream(dev).cuda_stream), h, "chore_render_fwd")
+    ws = _workspace(dev, _lib.lib.chore_render_workspace_bytes, "render", B=B, F=Fn, image_size=S, ssaa=ssaa)
+    rgb, depth, alpha, fim = _outputs(dev, B, S, ssaa, return_index)
+    _lib.check(_lib.lib.chore_render_fwd(h, tri.data_ptr(), tex.data_ptr(), _ptr(lt), B, Fn, tex.shape[2], S, ssaa, float(near),
+                                         float(far), float(eps), _background(background_color), rgb.data_ptr(), depth.data_ptr(),
+                                         alpha.data_ptr(), _ptr(fim), ws.data_ptr(), _stream(dev)), h, "chore_render_fwd")
     return rgb, depth, alpha, fim
 
 
@@ -201,8 +238,7 @@ def rasterize_rgbad(faces, textures, light=None, image_size=256, anti_aliasing=T
             raise ValueError("light (B,F,3) expected")
     ssaa, S = (2 if anti_aliasing else 1), int(image_size)
     if need_grad:
-        if _lib.lib.chore_render_workspace_bytes(B, Fn, S, ssaa) == 0:
-            raise ValueError("unsupported render shape B=%d F=%d image_size=%d ssaa=%d" % (B, Fn, S, ssaa))
+        _workspace(None, _lib.lib.chore_render_workspace_bytes, "render", B=B, F=Fn, image_size=S, ssaa=ssaa)
         rgb, depth, alpha, fim = _RasterizeRGBAD.apply(tri, tex, lt, S, ssaa, near, far, eps, background_color)
     else:
         rgb, depth, alpha, fim = _render_fwd(tri, tex, lt, S, ssaa, near, far, eps, background_color, return_index)
@@ -228,18 +264,8 @@ def splat_points(points_ndc, colors=None, radius=2.0, image_size=256, anti_alias
         raise ValueError("points_ndc (B,N,3) expected, got %s" % (tuple(pts.shape),))
     B, N = pts.shape[:2]
     ssaa, S = (2 if anti_aliasing else 1), int(image_size)
-    col = None
-    if colors is not None:
-        col = colors.detach().to(dev).float().contiguous()
-        if tuple(col.shape) != (B, N, 3):
-            raise ValueError("colors (B,N,3) expected, got %s" % (tuple(col.shape),))
-    rad, radius_px = None, 0.0
-    if torch.is_tensor(radius) and radius.dim() > 0:
-        rad = radius.detach().to(dev).float().contiguous()
-        if tuple(rad.shape) != (B, N):
-            raise ValueError("radius: a number or (B,N) expected, got %s" % (tuple(rad.shape),))
-    else:
-        radius_px = float(radius)
+    col = _opt(colors, dev, (B, N, 3), "colors", "(B,N,3)")
+    rad, radius_px = _radius(radius, dev, B, N, "(B,N)")
     if N == 0:
         bgc = torch.tensor([float(c) for c in background_color], dtype=torch.float32, device=dev)
         out = {"rgb": bgc.view(1, 3, 1, 1).expand(B, 3, S, S).contiguous(),
@@ -249,20 +275,11 @@ def splat_points(points_ndc, colors=None, radius=2.0, image_size=256, anti_alias
             out["point_index"] = torch.full((B, S * ssaa, S * ssaa), -1, dtype=torch.int32, device=dev)
         return out
     h = _lib.handle(dev.index or 0)
-    nbytes = _lib.lib.chore_splat_workspace_bytes(B, N, S, ssaa)
-    if nbytes == 0:
-        raise ValueError("unsupported splat shape B=%d N=%d image_size=%d ssaa=%d" % (B, N, S, ssaa))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    rgb = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
-    depth = torch.empty(B, S, S, dtype=torch.float32, device=dev)
-    alpha = torch.empty(B, S, S, dtype=torch.float32, device=dev)
-    pim = torch.empty(B, S * ssaa, S * ssaa, dtype=torch.int32, device=dev) if return_index else None
-    bg = (ctypes.c_float * 3)(*[float(c) for c in background_color])
-    _lib.check(_lib.lib.chore_splat_fwd(h, pts.data_ptr(), col.data_ptr() if col is not None else None,
-                                        rad.data_ptr() if rad is not None else None, radius_px, B, N, S, ssaa, float(ambient),
-                                        float(near), float(far), bg, rgb.data_ptr(), depth.data_ptr(), alpha.data_ptr(),
-                                        pim.data_ptr() if return_index else None, ws.data_ptr(),
-                                        torch.cuda.current_stream(dev).cuda_stream), h, "chore_splat_fwd")
+    ws = _workspace(dev, _lib.lib.chore_splat_workspace_bytes, "splat", B=B, N=N, image_size=S, ssaa=ssaa)
+    rgb, depth, alpha, pim = _outputs(dev, B, S, ssaa, return_index)
+    _lib.check(_lib.lib.chore_splat_fwd(h, pts.data_ptr(), _ptr(col), _ptr(rad), radius_px, B, N, S, ssaa, float(ambient),
+                                        float(near), float(far), _background(background_color), rgb.data_ptr(), depth.data_ptr(),
+                                        alpha.data_ptr(), _ptr(pim), ws.data_ptr(), _stream(dev)), h, "chore_splat_fwd")
     out = {"rgb": rgb, "depth": depth, "alpha": alpha}
     if return_index:
         out["point_index"] = pim
@@ -300,11 +317,7 @@ def rasterize_scene(faces, textures, light, points_ndc, colors=None, radius=2.0,
         raise ValueError("faces (B,F,3,3) and points_ndc (B,N,3) of one batch size expected, got %s and %s"
                          % (tuple(tri.shape), tuple(pts.shape)))
     B, Fn, N = tri.shape[0], tri.shape[1], pts.shape[1]
-    grp = None
-    if face_group is not None:
-        if torch.is_floating_point(face_group) or tuple(face_group.shape) != (B, Fn):
-            raise ValueError("face_group: integers %s expected, got %s %s" % ((B, Fn), face_group.dtype, tuple(face_group.shape)))
-        grp = face_group.detach().to(dev).to(torch.int32).contiguous()
+    grp = _face_group(face_group, dev, B, Fn)
     if Fn == 0:
         out = splat_points(pts, colors, radius, image_size, anti_aliasing, near, far, ambient, background_color, return_index)
         if return_index:
@@ -323,40 +336,20 @@ def rasterize_scene(faces, textures, light, points_ndc, colors=None, radius=2.0,
     ts = tex.shape[2]
     if tuple(tri.shape) != (B, Fn, 3, 3) or tuple(tex.shape) != (B, Fn, ts, ts, ts, 3):
         raise ValueError("faces (B,F,3,3) and textures (B,F,ts,ts,ts,3) expected, got %s and %s" % (tuple(tri.shape), tuple(tex.shape)))
-
-    def opt(x, shape, what):
-        if x is None:
-            return None
-        x = x.detach().to(dev).float().contiguous()
-        if tuple(x.shape) != shape:
-            raise ValueError("%s %s expected, got %s" % (what, shape, tuple(x.shape)))
-        return x
-    lt, col = opt(light, (B, Fn, 3), "light"), opt(colors, (B, N, 3), "colors")
-    op = opt(face_opacity, (B, Fn), "face_opacity")
-    rad, radius_px = None, 0.0
-    if torch.is_tensor(radius) and radius.dim() > 0:
-        rad = opt(radius, (B, N), "radius: a number or")
-    else:
-        radius_px = float(radius)
+    lt, col = _opt(light, dev, (B, Fn, 3), "light"), _opt(colors, dev, (B, N, 3), "colors")
+    op = _opt(face_opacity, dev, (B, Fn), "face_opacity")
+    rad, radius_px = _radius(radius, dev, B, N)
     ssaa, S = (2 if anti_aliasing else 1), int(image_size)
     h = _lib.handle(dev.index or 0)
-    nbytes = _lib.lib.chore_scene_workspace_bytes(B, Fn, N, S, ssaa)
-    if nbytes == 0:
-        raise ValueError("unsupported scene shape B=%d F=%d N=%d image_size=%d ssaa=%d" % (B, Fn, N, S, ssaa))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    rgb = torch.empty(B, 3, S, S, dtype=torch.float32, device=dev)
-    depth = torch.empty(B, S, S, dtype=torch.float32, device=dev)
-    alpha = torch.empty(B, S, S, dtype=torch.float32, device=dev)
-    sid = torch.empty(B, S * ssaa, S * ssaa, dtype=torch.int32, device=dev) if return_index else None
-    bg = (ctypes.c_float * 3)(*[float(c) for c in background_color])
-    ptr = lambda x: x.data_ptr() if x is not None else None      # noqa: E731
-    head = (h, tri.data_ptr(), tex.data_ptr(), ptr(lt), ptr(op), B, Fn, ts, pts.data_ptr(), ptr(col), ptr(rad), radius_px, N, bias, S,
-            ssaa, float(ambient), float(near), float(far), float(eps), bg)
-    tail = (rgb.data_ptr(), depth.data_ptr(), alpha.data_ptr(), ptr(sid), ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    ws = _workspace(dev, _lib.lib.chore_scene_workspace_bytes, "scene", B=B, F=Fn, N=N, image_size=S, ssaa=ssaa)
+    rgb, depth, alpha, sid = _outputs(dev, B, S, ssaa, return_index)
+    head = (h, tri.data_ptr(), tex.data_ptr(), _ptr(lt), _ptr(op), B, Fn, ts, pts.data_ptr(), _ptr(col), _ptr(rad), radius_px, N, bias,
+            S, ssaa, float(ambient), float(near), float(far), float(eps), _background(background_color))
+    tail = (rgb.data_ptr(), depth.data_ptr(), alpha.data_ptr(), _ptr(sid), ws.data_ptr(), _stream(dev))
     if layers == 1 and grp is None:
         _lib.check(_lib.lib.chore_scene_fwd(*head, *tail), h, "chore_scene_fwd")
     else:
-        _lib.check(_lib.lib.chore_scene_layers_fwd(*head, ptr(grp), layers, *tail), h, "chore_scene_layers_fwd")
+        _lib.check(_lib.lib.chore_scene_layers_fwd(*head, _ptr(grp), layers, *tail), h, "chore_scene_layers_fwd")
     out = {"rgb": rgb, "depth": depth, "alpha": alpha}
     if return_index:
         out["sample_id"] = sid
@@ -385,27 +378,18 @@ def rasterize_instances(faces, face_group=None, num_groups=1, image_size=256, an
     if tri.dim() != 4 or tuple(tri.shape[2:]) != (3, 3):
         raise ValueError("faces (B,F,3,3) expected, got %s" % (tuple(tri.shape),))
     B, Fn = tri.shape[:2]
-    grp = None
-    if face_group is not None:
-        if torch.is_floating_point(face_group) or tuple(face_group.shape) != (B, Fn):
-            raise ValueError("face_group: integers %s expected, got %s %s" % ((B, Fn), face_group.dtype, tuple(face_group.shape)))
-        grp = face_group.detach().to(dev).to(torch.int32).contiguous()
+    grp = _face_group(face_group, dev, B, Fn)
     ssaa, S = (2 if anti_aliasing else 1), int(image_size)
     h = _lib.handle(dev.index or 0)
-    nbytes = _lib.lib.chore_instances_workspace_bytes(B, Fn, G, S, ssaa)
-    if nbytes == 0:
-        raise ValueError("unsupported instances shape B=%d F=%d G=%d image_size=%d ssaa=%d" % (B, Fn, G, S, ssaa))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = _workspace(dev, _lib.lib.chore_instances_workspace_bytes, "instances", B=B, F=Fn, G=G, image_size=S, ssaa=ssaa)
     visible = torch.empty(B, G, S, S, dtype=torch.float32, device=dev)
     full = torch.empty(B, G, S, S, dtype=torch.float32, device=dev)
     face_samples = torch.empty(B, Fn, dtype=torch.int32, device=dev)
     group_samples = torch.empty(B, G, 2, dtype=torch.int32, device=dev)
     fim = torch.empty(B, S * ssaa, S * ssaa, dtype=torch.int32, device=dev) if return_index else None
-    _lib.check(_lib.lib.chore_instances_fwd(h, tri.data_ptr(), grp.data_ptr() if grp is not None else None, B, Fn, G, S, ssaa,
-                                            float(near), float(far), visible.data_ptr(), full.data_ptr(),
-                                            face_samples.data_ptr(), group_samples.data_ptr(),
-                                            fim.data_ptr() if return_index else None, ws.data_ptr(),
-                                            torch.cuda.current_stream(dev).cuda_stream), h, "chore_instances_fwd")
+    _lib.check(_lib.lib.chore_instances_fwd(h, tri.data_ptr(), _ptr(grp), B, Fn, G, S, ssaa, float(near), float(far),
+                                            visible.data_ptr(), full.data_ptr(), face_samples.data_ptr(), group_samples.data_ptr(),
+                                            _ptr(fim), ws.data_ptr(), _stream(dev)), h, "chore_instances_fwd")
     out = {"visible": visible, "full": full, "face_samples": face_samples, "group_samples": group_samples}
     if return_index:
         out["face_index"] = fim
