@@ -79,6 +79,12 @@ __device__ __forceinline__ double stat_read(const StatCell* c, size_t hi_cells) 
 // statistics of an activation tensor: [2 tables][B][32] GroupStat
 inline size_t act_stats_bytes(int B) { return (size_t)2 * B * GN_GROUPS * sizeof(GroupStat); }
 __host__ __device__ inline size_t act_hi_cells(int B) { return (size_t)B * GN_GROUPS * 2; }
+// the channel counts of the statistics kernels: a multiple of 32 from 32 to 256 whose group size C / 32 is a power of two (the xor
+// tree of group_lane_sum below mixes neighbouring groups otherwise: C = 96, 160, 192, 224)
+inline bool gn_channels_ok(int C) {
+    const int gs = C / GN_GROUPS;
+    return C >= GN_GROUPS && C <= 256 && C % GN_GROUPS == 0 && (gs & (gs - 1)) == 0;
+}
 // sum over the gs (power of two <= 8) consecutive channels of a group held by gs consecutive lanes: fixed tree
 __device__ __forceinline__ float group_lane_sum(float v, int gs) {
     for (int o = 1; o < gs; o <<= 1) v += __shfl_xor(v, o, 64);

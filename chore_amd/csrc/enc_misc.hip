@@ -98,6 +98,7 @@ __global__ void pack_stem_kernel(int Cin, const float* __restrict__ w, float* __
 }
 
 int launch_pack_stem(chore_handle* h, int Cin, const float* w, float* dst, hipStream_t s) {
+    if (Cin > STEM_MAXC) CHORE_FAIL(h, CHORE_EINVAL, "stem: Cin > %d", STEM_MAXC);      // before anything is written: launch_stem refuses it too
     const int n = Cin * 49 * 64;
     hipLaunchKernelGGL(pack_stem_kernel, dim3((n + 255) / 256), dim3(256), 0, s, Cin, w, dst);
     CHORE_LAUNCH_CHECK(h, s);
@@ -399,7 +400,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ x, 
 }
 
 int launch_gn_stats(chore_handle* h, int dtype, const View& x, int B, int HW, GroupStat* st, hipStream_t s) {
-    if (x.C % GN_GROUPS || x.C > 256 || x.C < 32) CHORE_FAIL(h, CHORE_EINVAL, "gn: unsupported C=%d", x.C);
+    if (!gn_channels_ok(x.C)) CHORE_FAIL(h, CHORE_EINVAL, "gn: unsupported C=%d", x.C);
     const int S = gn_splits(HW);
     dim3 grid(S, B);
     if (dtype == CHORE_F16)
@@ -474,7 +475,7 @@ __global__ __launch_bounds__(256) void gn_apply_relu_kernel(const T* __restrict_
 // powers of two)
 int launch_gn_apply_relu(chore_handle* h, int dtype, const View& x, const GroupStat* st, const float* gamma,
                          const float* beta, const View& y, int B, int HW, hipStream_t s, GroupStat* st_out) {
-    if (x.C > 256 || x.C % GN_GROUPS) CHORE_FAIL(h, CHORE_EINVAL, "gn: unsupported C=%d", x.C);
+    if (!gn_channels_ok(x.C)) CHORE_FAIL(h, CHORE_EINVAL, "gn: unsupported C=%d", x.C);
     const size_t total4 = (size_t)HW * (x.C / 4);
     int blocks = (int)((total4 + 255) / 256);
     if (blocks > 1024) blocks = 1024;
@@ -812,7 +813,7 @@ __global__ __launch_bounds__(256) void up2_bwd_kernel(const T* __restrict__ dy, 
 }
 
 int launch_up2_bwd(chore_handle* h, int dtype, const void* dy, void* dlow, int B, int H, int W, int C, hipStream_t s) {
-    if (C % 4 || H < 2 || W < 2) CHORE_FAIL(h, CHORE_EINVAL, "up2_bwd: unsupported shape");
+    if (B <= 0 || C <= 0 || C % 4 || H < 2 || W < 2) CHORE_FAIL(h, CHORE_EINVAL, "up2_bwd: unsupported shape");
     const size_t total4 = (size_t)B * H * W * (C / 4);
     const unsigned blocks = (unsigned)((total4 + 255) / 256);
     if (dtype == CHORE_F32)
@@ -843,7 +844,7 @@ __global__ __launch_bounds__(256) void pool2_bwd_kernel(const T* __restrict__ dy
 }
 
 int launch_pool2_bwd(chore_handle* h, int dtype, const void* dy, void* dx, int B, int H, int W, int C, hipStream_t s) {
-    if (C % 4 || (H & 1) || (W & 1)) CHORE_FAIL(h, CHORE_EINVAL, "pool2_bwd: unsupported shape");
+    if (C <= 0 || C % 4 || (H & 1) || (W & 1)) CHORE_FAIL(h, CHORE_EINVAL, "pool2_bwd: unsupported shape");
     const size_t total4 = (size_t)B * H * W * (C / 4);
     const unsigned blocks = (unsigned)((total4 + 255) / 256);
     if (dtype == CHORE_F32)

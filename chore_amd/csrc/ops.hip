@@ -35,10 +35,13 @@ int chore_gn_stats(chore_handle* h, int dtype, const void* x, int B, int HW, int
                    chore_stream_t stream) {
     CHORE_ENTER(h);
     if (!x || !stats || B <= 0 || HW <= 0) CHORE_FAIL(h, CHORE_EINVAL, "chore_gn_stats: bad argument");
+    dtype = elem_dtype(dtype);
+    if (dtype != CHORE_F32 && dtype != CHORE_BF16 && dtype != CHORE_F16) CHORE_FAIL(h, CHORE_EINVAL, "chore_gn_stats: dtype");
+    if (!gn_channels_ok(C)) CHORE_FAIL(h, CHORE_EINVAL, "chore_gn_stats: unsupported C=%d", C);      // before the accumulators are cleared
     hipStream_t s = (hipStream_t)stream;
     if (!zeroed) CHORE_HIP_CHECK(h, hipMemsetAsync(stats, 0, chore_gn_stats_bytes(B), s));
     View v; v.p = const_cast<void*>(x); v.cs = C; v.co = 0; v.C = C;
-    return launch_gn_stats(h, elem_dtype(dtype), v, B, HW, (GroupStat*)stats, s);
+    return launch_gn_stats(h, dtype, v, B, HW, (GroupStat*)stats, s);
 }
 
 // y = relu(groupnorm(x))
@@ -46,9 +49,13 @@ int chore_gn_relu_fwd(chore_handle* h, int dtype, const void* x, const void* sta
                       void* y, int B, int HW, int C, chore_stream_t stream) {
     CHORE_ENTER(h);
     if (!x || !stats || !gamma || !beta || !y) CHORE_FAIL(h, CHORE_EINVAL, "chore_gn_relu_fwd: null argument");
+    if (B <= 0 || HW <= 0) CHORE_FAIL(h, CHORE_EINVAL, "chore_gn_relu_fwd: bad shape");
+    dtype = elem_dtype(dtype);
+    if (dtype != CHORE_F32 && dtype != CHORE_BF16 && dtype != CHORE_F16) CHORE_FAIL(h, CHORE_EINVAL, "chore_gn_relu_fwd: dtype");
+    if (!gn_channels_ok(C)) CHORE_FAIL(h, CHORE_EINVAL, "chore_gn_relu_fwd: unsupported C=%d", C);
     View vx; vx.p = const_cast<void*>(x); vx.cs = C; vx.co = 0; vx.C = C;
     View vy; vy.p = y; vy.cs = C; vy.co = 0; vy.C = C;
-    return launch_gn_apply_relu(h, elem_dtype(dtype), vx, (const GroupStat*)stats, gamma, beta, vy, B, HW, (hipStream_t)stream);
+    return launch_gn_apply_relu(h, dtype, vx, (const GroupStat*)stats, gamma, beta, vy, B, HW, (hipStream_t)stream);
 }
 
 // y (B,H,W,Cout) = conv_{taps}(a) + bias, a = relu(groupnorm(x)) if stats != NULL else x; stride 1, zero padding.
@@ -190,17 +197,22 @@ int chore_upadd_fwd(chore_handle* h, int dtype, const void* a, const void* low, 
                     void* out_stats, chore_stream_t stream) {
     CHORE_ENTER(h);
     if (!a || !low || !y) CHORE_FAIL(h, CHORE_EINVAL, "chore_upadd_fwd: null argument");
+    if (B <= 0 || H <= 0 || W <= 0) CHORE_FAIL(h, CHORE_EINVAL, "chore_upadd_fwd: bad shape");
+    dtype = elem_dtype(dtype);
+    if (dtype != CHORE_F32 && dtype != CHORE_BF16 && dtype != CHORE_F16) CHORE_FAIL(h, CHORE_EINVAL, "chore_upadd_fwd: dtype");
     View va; va.p = const_cast<void*>(a); va.cs = C; va.co = 0; va.C = C;
     View vl; vl.p = const_cast<void*>(low); vl.cs = C; vl.co = 0; vl.C = C;
     View vy; vy.p = y; vy.cs = C; vy.co = 0; vy.C = C;
-    return launch_upadd(h, elem_dtype(dtype), va, vl, vy, B, H, W, (GroupStat*)out_stats, (hipStream_t)stream);
+    return launch_upadd(h, dtype, va, vl, vy, B, H, W, (GroupStat*)out_stats, (hipStream_t)stream);
 }
 
 // d_low (B,H,W,C) = transpose of the bicubic x2 upsampling applied to dy (B,2H,2W,C)
 int chore_up2_bwd(chore_handle* h, int dtype, const void* dy, void* dlow, int B, int H, int W, int C, chore_stream_t stream) {
     CHORE_ENTER(h);
     if (!dy || !dlow) CHORE_FAIL(h, CHORE_EINVAL, "chore_up2_bwd: null argument");
-    return launch_up2_bwd(h, elem_dtype(dtype), dy, dlow, B, H, W, C, (hipStream_t)stream);
+    dtype = elem_dtype(dtype);
+    if (dtype != CHORE_F32 && dtype != CHORE_BF16) CHORE_FAIL(h, CHORE_EINVAL, "chore_up2_bwd: dtype");
+    return launch_up2_bwd(h, dtype, dy, dlow, B, H, W, C, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -242,11 +242,9 @@ def test_conv_block_operator(dtype, cin, cout, shape):
             check(p.grad, ref[n].grad, dtype, f"block{i}.{n}")
     # the statistics handed on are those of a fresh statistics pass over y1 (two-limb fixed-point sums of per-workgroup
     # fp32 partials in both: equal up to the grouping of those partials).  Layout (csrc/enc_common.h): two tables of
-    # 16-byte cells, value = (table1.hi * 2^32 + table0.lo) * 2^-40
-    def decode(t):
-        w = t.cpu().numpy().view(np.uint64).reshape(2, -1, 2)
-        return w[0, :, 0].astype(np.float64) + w[1, :, 1].view(np.int64).astype(np.float64) * 2.0 ** 32
-    a, b = decode(s1), decode(ops.gn_stats(y1.detach())[:s1.numel()])
+    # 16-byte cells, value = (table1.hi * 2^32 + table0.lo) * 2^-40: decoded by tests/map_ref.py
+    from map_ref import stats_cells
+    a, b = stats_cells(s1), stats_cells(ops.gn_stats(y1.detach())[:s1.numel()])
     assert np.abs(a - b).max() <= 1e-6 * np.abs(b).max()
 
 
