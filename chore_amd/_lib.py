@@ -201,6 +201,17 @@ SIGNATURES = {
     "chore_silhouette_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p,
                                      c_void_p, c_void_p]),
     "chore_silhouette_bwd": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
+    "chore_edt_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "chore_edt_sq": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "chore_edt_sqrt_f64": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "chore_edt_tiles": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "chore_sil_edge_edt_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "chore_sil_edge_edt": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "chore_sil_targets_workspace_bytes": (c_size_t, [c_int]),
+    "chore_sil_targets": (c_int, [c_void_p] * 4 + [c_int] * 4 + [ctypes.c_double, ctypes.c_double, c_int] + [c_void_p] * 7),
+    "chore_sil_edge_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "chore_sil_edge_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "chore_sil_edge_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "chore_render_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "chore_render_fwd": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_float] * 3 + [c_void_p] * 7),
     "chore_render_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),

@@ -16,6 +16,10 @@ detectron2's BitMasks.crop_and_resize and builds the ROI intrinsics from the Kin
 / torch (bounding box of the mask, PHOSA's make_bbox_square, bilinear crop sampled at pixel centres, threshold 0.5).
 That preprocessing is setup code outside the fitting loop and its parity with detectron2 is NOT pinned; callers
 that already own the cropped masks can pass them with `SilLossROI.from_crops`.
+
+`SilLossROI.from_masks` / `set_masks` do the constructor's work on the device without a host round trip (csrc/sil_targets.hip:
+chore_sil_targets, chore_sil_edge_edt), so a kept fitting chain refreshes its term inside recorded graphs; `edge_loss` is
+PHOSA's edge term on `edt_ref_edge` (chore_sil_edge_fwd / _bwd), an opt-in term of the 'sil' phase that the reference does not have.
 """
 import os
 
@@ -97,6 +101,41 @@ class _PlacedTrianglesFn(torch.autograd.Function):
                                                   adj.data_ptr(), g.data_ptr(), dR.data_ptr(), dt.data_ptr(), ds.data_ptr(),
                                                   torch.cuda.current_stream(dev).cuda_stream), h, "chore_sil_project_bwd")
         return (dR, dt, ds) + (None,) * 7
+
+
+class _EdgeTermFn(torch.autograd.Function):
+    """image, weight (B,S,S) -> (B) sums of (maxpool_k(image) - image) * weight; gradient for the image only"""
+
+    @staticmethod
+    def forward(ctx, image, weight, ksize):
+        if not image.is_cuda:
+            raise RuntimeError("chore_amd needs device tensors (no CPU path)")
+        dev = image.device
+        h = _lib.handle(dev.index or 0)
+        img, w = image.detach().float().contiguous(), weight.detach().float().contiguous()
+        B, S = img.shape[:2]
+        if img.dim() != 3 or img.shape[2] != S or w.shape != img.shape:
+            raise ValueError("edge term: (B,S,S) image and weight expected, got %s and %s" % (tuple(img.shape), tuple(w.shape)))
+        sums = torch.empty(B, dtype=torch.float32, device=dev)
+        arg = torch.empty(B, S, S, dtype=torch.int32, device=dev)
+        ws = torch.empty(max(_lib.lib.chore_sil_edge_workspace_bytes(B, S), 1), dtype=torch.uint8, device=dev)
+        _lib.check(_lib.lib.chore_sil_edge_fwd(h, img.data_ptr(), w.data_ptr(), B, S, ksize, sums.data_ptr(), arg.data_ptr(),
+                                               ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), h, "chore_sil_edge_fwd")
+        ctx.save_for_backward(w, arg)
+        ctx.ksize = ksize
+        return sums
+
+    @staticmethod
+    def backward(ctx, g):
+        w, arg = ctx.saved_tensors
+        dev = w.device
+        h = _lib.handle(dev.index or 0)
+        B, S = w.shape[:2]
+        g = g.float().contiguous()
+        gi = torch.empty_like(w)
+        _lib.check(_lib.lib.chore_sil_edge_bwd(h, w.data_ptr(), arg.data_ptr(), g.data_ptr(), B, S, ctx.ksize, gi.data_ptr(),
+                                               torch.cuda.current_stream(dev).cuda_stream), h, "chore_sil_edge_bwd")
+        return gi, None, None
 
 
 def corner_adjacency(faces, num_verts):
@@ -225,11 +264,14 @@ class SilLossROI(nn.Module):
         self.register_buffer("keep_mask", self.cvt_masks(ps_crop, obj_crop).float())
         self.pool = nn.MaxPool2d(kernel_size=kernel_size, stride=1, padding=kernel_size // 2)
         self.prepare_dist_trans(self.image_ref)
+        self.register_buffer("K", Ks)
+        self._setup_template(temp_verts, temp_faces, B, dev)
+
+    def _setup_template(self, temp_verts, temp_faces, B, dev):
         verts = torch.as_tensor(np.asarray(temp_verts), dtype=torch.float32)
         faces = torch.as_tensor(np.asarray(temp_faces).astype(np.int64))
         self.register_buffer("vertices", verts.repeat(B, 1, 1).to(dev))
         self.register_buffer("faces", faces.repeat(B, 1, 1).to(dev))
-        self.register_buffer("K", Ks)
         self.register_buffer("R", torch.eye(3, device=dev).unsqueeze(0))
         self.register_buffer("t", torch.zeros(1, 3, device=dev))
         # for the one-launch placement + projection (_PlacedTrianglesFn): int32 faces and the corner lists of the vertices
@@ -237,6 +279,63 @@ class SilLossROI(nn.Module):
         self.register_buffer("faces32", self.faces.to(torch.int32).contiguous(), persistent=False)
         self.register_buffer("adj_off", torch.from_numpy(off).to(dev), persistent=False)
         self.register_buffer("adj", torch.from_numpy(ent).to(dev), persistent=False)
+
+    @classmethod
+    def from_masks(cls, person_masks, obj_masks, temp_mesh, crop_centers, rend_size=256, kernel_size=7, bbox_expansion=0.3,
+                   device="cuda:0", crop_size=1200):
+        """the constructor's arguments and buffers, filled on the device (chore_sil_targets, chore_sil_edge_edt) without a host
+        synchronisation: nothing is downloaded, no device value is read on the host.  One more buffer, `valid` (B) int32, and
+        `box_sq` (B,4) float64, the square boxes.  Differences from the constructor: the crops' coordinates and weights are
+        computed in float64 (the constructor's grid_sample runs in float32, so a pixel whose value lies within float32 round-off
+        of the 0.5 threshold can differ); and a frame whose object mask is EMPTY cannot raise ValueError as the constructor does,
+        for that would need a synchronisation -- it gets valid = 0, all-zero image_ref and keep_mask (its mask term is 0) and the
+        finite K of the whole image.  Check `valid` where an empty mask is an error."""
+        self = cls.__new__(cls)
+        nn.Module.__init__(self)
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("chore_amd needs device tensors (no CPU path)")
+        temp_verts, temp_faces = (temp_mesh.v, temp_mesh.f) if hasattr(temp_mesh, "v") else temp_mesh
+        obj_masks = torch.as_tensor(obj_masks)
+        B, S = obj_masks.shape[0], int(rend_size)
+        self.rend_size, self.kernel_size = S, int(kernel_size)
+        self.bbox_expansion, self.crop_size = float(bbox_expansion), float(crop_size)
+        self.pool = nn.MaxPool2d(kernel_size=kernel_size, stride=1, padding=kernel_size // 2)
+        for name in ("image_ref", "keep_mask", "edt_ref_edge"):
+            self.register_buffer(name, torch.empty(B, S, S, dtype=torch.float32, device=dev))
+        self.register_buffer("K", torch.empty(B, 3, 3, dtype=torch.float32, device=dev))
+        self.register_buffer("valid", torch.empty(B, dtype=torch.int32, device=dev))
+        self.register_buffer("box_sq", torch.empty(B, 4, dtype=torch.float64, device=dev))
+        # scratch of the two launches, kept: set_masks runs inside recorded graphs
+        self.register_buffer("ref_edges", torch.empty(B, S, S, dtype=torch.float32, device=dev), persistent=False)
+        nws = max(_lib.lib.chore_sil_targets_workspace_bytes(B), _lib.lib.chore_sil_edge_edt_workspace_bytes(B, S), 1)
+        self.register_buffer("_targets_ws", torch.empty(nws, dtype=torch.uint8, device=dev), persistent=False)
+        self._setup_template(temp_verts, temp_faces, B, dev)
+        return self.set_masks(person_masks, obj_masks, crop_centers)
+
+    @torch.no_grad()
+    def set_masks(self, person_masks, obj_masks, crop_centers):
+        """new masks (B,H,W) and crop centres (B,2) for an object built by from_masks: image_ref, keep_mask, K, valid, box_sq and
+        edt_ref_edge are refreshed IN PLACE (a recorded fitting step keeps reading these buffers), no host synchronisation"""
+        if not hasattr(self, "_targets_ws"):
+            raise RuntimeError("SilLossROI.set_masks: only for objects built by SilLossROI.from_masks")
+        dev = self.image_ref.device
+        B, S = self.image_ref.shape[:2]
+        prep = lambda a: torch.as_tensor(a).to(device=dev, dtype=torch.float32).contiguous()      # noqa: E731
+        person, obj, cc = prep(person_masks), prep(obj_masks), prep(crop_centers)
+        if obj.dim() != 3 or obj.shape[0] != B or person.shape != obj.shape or tuple(cc.shape) != (B, 2):
+            raise ValueError("SilLossROI.set_masks: (B,H,W) masks and (B,2) centres for B = %d expected, got %s, %s, %s"
+                             % (B, tuple(person.shape), tuple(obj.shape), tuple(cc.shape)))
+        h = _lib.handle(dev.index or 0)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(_lib.lib.chore_sil_targets(h, person.data_ptr(), obj.data_ptr(), cc.data_ptr(), B, obj.shape[1], obj.shape[2], S,
+                                              self.bbox_expansion, self.crop_size, self.net_input_size, self.image_ref.data_ptr(),
+                                              self.keep_mask.data_ptr(), self.K.data_ptr(), self.box_sq.data_ptr(),
+                                              self.valid.data_ptr(), self._targets_ws.data_ptr(), stream), h, "chore_sil_targets")
+        _lib.check(_lib.lib.chore_sil_edge_edt(h, self.image_ref.data_ptr(), B, S, self.kernel_size, 0.25, self.ref_edges.data_ptr(),
+                                               self.edt_ref_edge.data_ptr(), self._targets_ws.data_ptr(), stream), h,
+                   "chore_sil_edge_edt")
+        return self
 
     @torch.no_grad()
     def load_from(self, other):
@@ -308,6 +407,12 @@ class SilLossROI(nn.Module):
         """forward()[0] without the outputs the fitting loop does not read (the edge image costs a max-pool per step)"""
         image = self.keep_mask * self.render(R, obj_t, obj_s)
         return {"mask": torch.sum((image - self.image_ref) ** 2, dim=(1, 2)).mean()}, image
+
+    def edge_loss(self, image):
+        """PHOSA's edge term on the image mask_loss returns: {"edge": mean_b sum_pixels compute_edges(image) * edt_ref_edge},
+        forward and backward in one launch pair each (chore_sil_edge_fwd / _bwd).  Not a term of the reference's fit."""
+        k = self.pool.kernel_size
+        return {"edge": _EdgeTermFn.apply(image, self.edt_ref_edge, k if isinstance(k, int) else k[0]).mean()}
 
     def forward(self, R, obj_t, obj_s):
         loss_dict, image = self.mask_loss(R, obj_t, obj_s)

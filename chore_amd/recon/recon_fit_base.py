@@ -438,6 +438,18 @@ class ReconFitterBase:
     # False (the default): nothing is computed, no key appears, no fitted bit changes.
     PENETRATION_TERM = False
 
+    # True: optimize_smpl_object builds the silhouette term from the batch's masks with SilLossROI.from_masks (boxes, crops,
+    # intrinsics and the edge distance transform on the device, no host round trip) and a kept slot refreshes its term in place
+    # with set_masks.  The crops are then sampled in float64, not float32: pixels within round-off of the threshold can differ.
+    # False (the default): the host constructor, as before; no fitted bit changes.
+    SIL_DEVICE_SETUP = False
+    SIL_REND_SIZE = 256         # the term's rend_size when this class builds it (the reference's default)
+
+    # True: forward_step(..., "sil") adds loss_dict["edge"] = SilLossROI.edge_loss of the image the mask term rendered
+    # (PHOSA's sum(edges(rendered) * edt_ref_edge), which pulls the rendered outline onto the mask's), weighted by
+    # get_loss_weights()["edge"].  False (the default): nothing is computed, no key appears, no fitted bit changes.
+    SIL_EDGE_TERM = False
+
     def _template_closed(self):
         """is the template a closed mesh (is_closed)?  Checked on the host once per template -- before any step is recorded"""
         from .eval.penetration import is_closed

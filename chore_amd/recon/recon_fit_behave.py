@@ -205,7 +205,10 @@ class ReconFitterBehave(ReconFitterBase):
              "ocent": 15 ** 2, "collide": 3 ** 2, "pinit": 5 ** 2, "rot": 10.0 ** 2, "trans": 10.0 ** 2,
              # "pen" (PENETRATION_TERM, not in the reference): the coefficient this table gives the two other terms that are a
              # mean of distances in metres ("object", "df_h").  Not tuned.
-             "pen": 30.0 ** 2}
+             "pen": 30.0 ** 2,
+             # "edge" (SIL_EDGE_TERM, not in the reference): the coefficient this table gives "mask", the other term that is a
+             # sum over the pixels of the rendering.  Not tuned.
+             "edge": 0.003 ** 2}
         return {k: (lambda cst, it, c=c: c * cst / (1 + it)) for k, c in w.items()}
 
     # ---- the whole chain ------------------------------------------------------------------------------
@@ -728,10 +731,12 @@ class ReconFitterBehave(ReconFitterBase):
         R = self.project_so3(rot_noisy) if rot_noisy is not None else self.decopose_axis(obj_R, noise=noise)
         if phase == "sil":      # none of its terms reads the field (the reference queries the object points all the same, :171)
             sil = data_dict["silhouette"]
-            obj_losses = sil.mask_loss(R, obj_t, obj_s)[0] if hasattr(sil, "mask_loss") else sil(R, obj_t, obj_s)[0]
+            obj_losses, image = sil.mask_loss(R, obj_t, obj_s) if hasattr(sil, "mask_loss") else sil(R, obj_t, obj_s)[:2]
             loss_dict["mask"] = obj_losses["mask"]
             loss_dict["scale"] = torch.mean((obj_s - self.obj_scale) ** 2)
             loss_dict["trans"] = torch.mean((obj_t - data_dict["trans_init"]) ** 2)
+            if self.SIL_EDGE_TERM:         # opt-in: PHOSA's edge term on the image the mask term rendered
+                loss_dict["edge"] = sil.edge_loss(image)["edge"]
             return loss_dict
         object = self.transform_obj_verts(data_dict["objects"], R, obj_t, obj_s)
         model.query(object, **data_dict["query_dict"])
@@ -778,13 +783,17 @@ class ReconFitterBehave(ReconFitterBase):
         smpl = data_dict["smpl"]
         split = self.split_smpl(smpl)
         data_dict["smpl"] = split
+        sil_masks = None        # SIL_DEVICE_SETUP: the term is built (or a kept one refreshed in place) once the slot is known
         if "silhouette" not in data_dict and self.scan is not None and "images" in data_dict:
             from .obj_pose_roi import SilLossROI
             images = data_dict["images"]
-            data_dict["silhouette"] = SilLossROI(images[:, 3, :, :], images[:, 4, :, :], self.scan,
-                                                 data_dict["query_dict"]["crop_center"], device=self.device,
-                                                 crop_size=self.camera.crop_size).to(self.device)
-        if "silhouette" not in data_dict:
+            if self.SIL_DEVICE_SETUP:
+                sil_masks = (images[:, 3, :, :], images[:, 4, :, :], data_dict["query_dict"]["crop_center"])
+            else:
+                data_dict["silhouette"] = SilLossROI(images[:, 3, :, :], images[:, 4, :, :], self.scan,
+                                                     data_dict["query_dict"]["crop_center"], rend_size=self.SIL_REND_SIZE,
+                                                     device=self.device, crop_size=self.camera.crop_size).to(self.device)
+        if "silhouette" not in data_dict and sil_masks is None:
             sil_iter = 0
         data_dict["smpl_center"] = self.compute_smpl_center_pred(data_dict, model, smpl)
         # no optimiser of this function owns a SMPL parameter (reference quirk, :102,126,134): their gradients would be
@@ -804,10 +813,20 @@ class ReconFitterBehave(ReconFitterBase):
         sil = data_dict.get("silhouette")
         slot = None
         if obj_R.is_cuda and (sil is None or hasattr(sil, "load_from")):
+            sil_key = None if sil is None else (type(sil).__name__, tuple(getattr(sil, "image_ref", torch.empty(0)).shape))
+            if sil_masks is not None:
+                sil_key = ("SilLossROI", (obj_R.shape[0], self.SIL_REND_SIZE, self.SIL_REND_SIZE))
             slot = self._slot("object", tuple(obj_R.shape), tuple(data_dict["objects"].shape), tuple(body.shape), str(obj_R.device),
-                              self._maps_key(model), obj_iter, joint_iter, steps_per_iter, sil_iter, max_iter,
-                              None if sil is None else (type(sil).__name__, tuple(getattr(sil, "image_ref", torch.empty(0)).shape)),
-                              bool(self.PENETRATION_TERM))     # kept graphs of one setting are not replayed under the other
+                              self._maps_key(model), obj_iter, joint_iter, steps_per_iter, sil_iter, max_iter, sil_key,
+                              bool(self.PENETRATION_TERM),     # kept graphs of one setting are not replayed under the other
+                              bool(self.SIL_DEVICE_SETUP), bool(self.SIL_EDGE_TERM))
+        if sil_masks is not None:
+            if slot is None or "silhouette" not in slot.objects:
+                sil = SilLossROI.from_masks(sil_masks[0], sil_masks[1], self.scan, sil_masks[2], rend_size=self.SIL_REND_SIZE,
+                                            device=self.device, crop_size=self.camera.crop_size)
+            else:                             # the kept term, refreshed in place: the recorded steps read its buffers
+                sil = slot.objects["silhouette"].set_masks(*sil_masks)
+            data_dict["silhouette"] = sil
         if slot is None:
             self._optimize_object(model, split, data_dict, None, obj_R, obj_t, obj_s, obj_iter, joint_iter, steps_per_iter,
                                   sil_iter, max_iter)

@@ -32,4 +32,6 @@ class ReconFitterCoco(ReconFitterBehave):
              "pinit": 10 ** 2, "ocent": 30 ** 2, "mask": 0.3 ** 2, "collide": 15 ** 2, "trans": 10.0 ** 2}
         if self.PENETRATION_TERM:       # not in the reference, whose table this is key for key: the opt-in term's coefficient as
             w["pen"] = 30.0 ** 2        # in recon_fit_behave.py (that of a mean of distances in metres there), not tuned
+        if self.SIL_EDGE_TERM:          # likewise not in the reference: the coefficient this table gives "mask", the other term
+            w["edge"] = 0.3 ** 2        # that is a sum over the pixels of the rendering, not tuned
         return {k: (lambda cst, it, c=c: c * cst / (1 + it)) for k, c in w.items()}

@@ -312,6 +312,53 @@ int chore_sil_project_bwd(chore_handle* h, const float* verts, const float* obj_
                           const float* g_tri, float* d_obj_R, float* d_obj_t, float* d_obj_s, chore_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The silhouette term's targets on the device, and PHOSA's edge term  (replaces the host work of SilLossROI's constructor,
+ * recon/obj_pose_roi.py:21-103,125-157: np.nonzero boxes, one grid_sample per frame, scipy's distance_transform_edt per frame).
+ * Every call is a fixed sequence of launches on `stream`, reads no device value on the host and allocates nothing: it can be
+ * captured into a graph.  Fills are kernels, atomics are integer only, float sums have a fixed order: same inputs, same bits.
+ *
+ * chore_edt_sq: feature (B,H,W) bytes -> d2 (B,H,W) int32, the exact squared Euclidean distance from every pixel to the
+ * nearest pixel of the same image whose feature byte is non-zero (integers throughout).  H, W <= 4096 (d2 < 2^25), anything
+ * larger is CHORE_EINVAL.  An image WITHOUT any feature pixel gets the sentinel 2 * max(H,W)^2 everywhere (larger than any real
+ * value; what scipy returns in that case is an artefact of its implementation and is not reproduced).  workspace:
+ * chore_edt_workspace_bytes (0 = unsupported shape).  chore_edt_sqrt_f64: out[i] = sqrt((double) d2[i]), correctly rounded.
+ * chore_edt_tiles: the column pass's columns per block, the row pass's threads per block, the largest H / W (host; for tests).
+ * ------------------------------------------------------------------------------------------- */
+size_t chore_edt_workspace_bytes(int B, int H, int W);
+int chore_edt_sq(chore_handle* h, const uint8_t* feature, int B, int H, int W, int* d2, void* workspace, chore_stream_t stream);
+int chore_edt_sqrt_f64(chore_handle* h, const int* d2, size_t n, double* out, chore_stream_t stream);
+int chore_edt_tiles(int* col_tile, int* row_tile, int* max_dim);
+/* What compute_edges and prepare_dist_trans produce from image_ref (B,S,S): edges = maxpool_k(image_ref) - image_ref (stride 1,
+ * padding k/2 that never wins, k odd <= 31) and edt = (float) sqrt(sqrt((double) d2)) for power == 0.25, in general
+ * (float) pow(sqrt((double) d2), 2 power), d2 = chore_edt_sq of the feature edges > 0 (its sentinel for a frame without edges). */
+size_t chore_sil_edge_edt_workspace_bytes(int B, int S);
+int chore_sil_edge_edt(chore_handle* h, const float* image_ref, int B, int S, int ksize, float power, float* edges, float* edt,
+                       void* workspace, chore_stream_t stream);
+/* person, obj (B,H,W) masks, crop_centers (B,2) ->
+ *   box_sq (B,4) double: make_bbox_square(xywh box of obj > 0.5, expansion) as x, y, s, s;  valid (B) int32: 1 if obj > 0.5 anywhere;
+ *   K (B,3,3): compute_K_roi(to_original_bbox(box_sq, crop_size / net_input_size, crop_center, crop_size)), computed in double
+ *     in the operation order of the Python functions, each operation rounded once, rounded to float at the end;
+ *   image_ref, keep_mask (B,S,S): the bilinear crops of obj / person over box_sq sampled at the output grid's pixel centres
+ *     x + (i + 0.5) s / S - 0.5 (coordinates and weights in double, zeros outside), thresholded at >= 0.5, then
+ *     image_ref = obj crop, keep_mask = obj crop or not person crop (cvt_masks).
+ * A frame whose object mask is empty gets valid = 0, all-zero image_ref and keep_mask (its mask term is 0) and the K of the
+ * box (0, 0, max(H,W), max(H,W)). */
+size_t chore_sil_targets_workspace_bytes(int B);
+int chore_sil_targets(chore_handle* h, const float* person, const float* obj, const float* crop_centers, int B, int H, int W,
+                      int S, double expansion, double crop_size, int net_input_size, float* image_ref, float* keep_mask, float* K,
+                      double* box_sq, int* valid, void* workspace, chore_stream_t stream);
+/* per_frame_sum[b] = sum_pixels (maxpool_k(image) - image) * weight, image / weight (B,S,S); argmax (B,S,S) int32 = y * S + x of
+ * the window's first maximum in row-major order (torch.max_pool2d's rule; NaN inputs are out of scope).  The sum is a tree over
+ * blocks of 256 pixels (8 additions deep), then per frame thread t adds block sums t, t + 256, ... and the same tree follows:
+ * the longest chain is 16 + ceil(ceil(S^2 / 256) / 256) additions.  workspace: chore_sil_edge_workspace_bytes.
+ * Backward, gather form: g_image[p] = g_per_frame[b] * (sum_{q: argmax[q] == p} weight[q] - weight[p]), q in row-major order. */
+size_t chore_sil_edge_workspace_bytes(int B, int S);
+int chore_sil_edge_fwd(chore_handle* h, const float* image, const float* weight, int B, int S, int ksize, float* per_frame_sum,
+                       int* argmax, void* workspace, chore_stream_t stream);
+int chore_sil_edge_bwd(chore_handle* h, const float* weight, const int* argmax, const float* g_per_frame, int B, int S, int ksize,
+                       float* g_image, chore_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Colour / depth / coverage rendering of meshes  (replaces what Renderer.render gets from neural_renderer's
  * rasterize_rgbad, external/neural_renderer/neural_renderer/rasterize.py:267-348: forward_face_index_map,
  * forward_texture_sampling, forward_background and forward_alpha_map of cuda/rasterize_cuda_kernel.cu:24-288 at image
