@@ -330,21 +330,22 @@ int chore_gen_surface_step_fused(chore_handle* h, const float* points, const flo
     return launch_query_bwd(h, plan_of(QUERY_SURFACE_STEP, dtype, x3, a), a, (hipStream_t)stream);
 }
 
-size_t chore_query_train_bytes(int B, int N) {
-    if (B <= 0 || N <= 0) return 0;
-    return (size_t)B * N * ((2 * QF_KPAD + 2 * 3 * HEAD_NUM * HEAD_HID) * sizeof(float) + 3 * HEAD_NUM * 2 * sizeof(unsigned long long)) +
-           2 * (size_t)B * scatter_sort_ints(N) * sizeof(int);
+// the staging of a training step (shapes in common.h, QueryArgs), nothing between its parts; returns its bytes
+static size_t train_staging(QueryArgs& a, void* staging) {
+    const size_t P = (size_t)a.B * a.N;
+    WsCarver c(staging);
+    a.tX = c.raw<float>(P * QF_KPAD); a.tH = c.raw<float>(P * 3 * HEAD_NUM * HEAD_HID);
+    a.tdZ = c.raw<float>(P * 3 * HEAD_NUM * HEAD_HID); a.tdX = c.raw<float>(P * QF_KPAD);
+    a.tM = c.raw<unsigned long long>(P * 3 * HEAD_NUM * 2);
+    a.tSort = c.raw<int>(2 * (size_t)a.B * scatter_sort_ints(a.N));
+    return c.bytes;
 }
 
-static void train_staging(QueryArgs& a, void* staging) {
-    const size_t P = (size_t)a.B * a.N;
-    float* f = (float*)staging;
-    a.tX = f;
-    a.tH = a.tX + P * QF_KPAD;
-    a.tdZ = a.tH + P * 3 * HEAD_NUM * HEAD_HID;
-    a.tdX = a.tdZ + P * 3 * HEAD_NUM * HEAD_HID;
-    a.tM = (unsigned long long*)(a.tdX + P * QF_KPAD);
-    a.tSort = (int*)(a.tM + P * 3 * HEAD_NUM * 2);
+size_t chore_query_train_bytes(int B, int N) {
+    if (B <= 0 || N <= 0) return 0;
+    QueryArgs a;
+    a.B = B; a.N = N;
+    return train_staging(a, nullptr);
 }
 
 // the query forward of a training step: as chore_query_fwd, and the 323-vectors and ReLU outputs of the hidden layers go

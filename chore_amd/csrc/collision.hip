@@ -43,31 +43,23 @@ struct CollWs {
     int cand_cap, pair_cap;
 };
 
-__host__ __device__ inline size_t al256(size_t n) { return (n + 255) / 256 * 256; }
 inline int coll_cand_cap(int F) { return F * 24 + 4096; }
 inline int coll_pair_cap(int F) { return F * 8 + 1024; }      // the reference's list length: F * max_collisions
 
-size_t coll_ws_layout(int B, int V, int F, char* base, CollWs* w) {
-    size_t o = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + o : nullptr; o += al256(bytes); return p; };
-    const int cc = coll_cand_cap(F), pc = coll_pair_cap(F);
-    char* box = take((size_t)B * F * 2 * sizeof(f32x4));
-    char* tbox = take((size_t)B * ((F + CT - 1) / CT) * 2 * sizeof(f32x4));
-    const size_t nt_ = (F + CT - 1) / CT, ntp = nt_ * (nt_ + 1) / 2;
-    char* tpair = take((size_t)B * ntp * sizeof(int2));
-    char* cand = take((size_t)B * cc * sizeof(int2));
-    char* pair = take((size_t)B * pc * sizeof(int2));
-    char* cnt = take((size_t)(3 * B + 2) * sizeof(unsigned));
-    char* lfx = take((size_t)B * sizeof(long long));
-    char* gfx = take((size_t)B * V * 3 * sizeof(long long));
-    if (w) {
-        w->box = (f32x4*)box; w->tbox = (f32x4*)tbox; w->cand = (int2*)cand; w->pair = (int2*)pair;
-        w->tpair = (int2*)tpair;
-        w->ncand = (unsigned*)cnt; w->npair = w->ncand + B; w->overflow = w->npair + B; w->ntpair = w->overflow + 2;
-        w->loss_fx = (long long*)lfx; w->grad_fx = (long long*)gfx;
-        w->cand_cap = cc; w->pair_cap = pc;
-    }
-    return o;
+// the layout in `base` (null: nothing but the size) -> *w; returns its bytes
+size_t coll_ws_layout(int B, int V, int F, void* base, CollWs* w) {
+    const size_t nt_ = (F + CT - 1) / CT;
+    WsCarver c(base);
+    w->cand_cap = coll_cand_cap(F); w->pair_cap = coll_pair_cap(F);
+    w->box = c.take<f32x4>((size_t)B * F * 2);
+    w->tbox = c.take<f32x4>((size_t)B * nt_ * 2);
+    w->tpair = c.take<int2>((size_t)B * (nt_ * (nt_ + 1) / 2));
+    w->cand = c.take<int2>((size_t)B * w->cand_cap);
+    w->pair = c.take<int2>((size_t)B * w->pair_cap);
+    w->ncand = c.raw<unsigned>(B); w->npair = c.raw<unsigned>(B); w->overflow = c.raw<unsigned>(2); w->ntpair = c.take<unsigned>(B);
+    w->loss_fx = c.take<long long>(B);
+    w->grad_fx = c.take<long long>((size_t)B * V * 3);
+    return c.bytes;
 }
 
 __global__ void coll_setup_kernel(const float* __restrict__ verts, const int* __restrict__ faces, int B, int V, int F, CollWs w) {
@@ -433,7 +425,8 @@ extern "C" {
 
 size_t chore_collision_workspace_bytes(int B, int V, int F) {
     if (B <= 0 || V <= 0 || F <= 0) return 0;
-    return coll_ws_layout(B, V, F, nullptr, nullptr);
+    CollWs w;
+    return coll_ws_layout(B, V, F, nullptr, &w);
 }
 
 int chore_collision_fwd(chore_handle* h, const float* verts, const int* faces, int B, int V, int F, float* loss, float* gverts,
@@ -443,7 +436,7 @@ int chore_collision_fwd(chore_handle* h, const float* verts, const int* faces, i
     if (B <= 0 || V <= 0 || F <= 0) CHORE_FAIL(h, CHORE_EINVAL, "chore_collision_fwd: B, V, F must be positive");
     hipStream_t s = (hipStream_t)stream;
     CollWs w;
-    coll_ws_layout(B, V, F, (char*)workspace, &w);
+    coll_ws_layout(B, V, F, workspace, &w);
     size_t n = (size_t)B * (F > V * 3 ? F : V * 3);
     if (n < (size_t)(3 * B + 2)) n = 3 * B + 2;
     hipLaunchKernelGGL(coll_setup_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, verts, faces, B, V, F, w);

@@ -164,6 +164,23 @@ inline int chore_launch(chore_handle* h, hipStream_t s, const char* file, int li
 }
 #define CHORE_LAUNCH(h, s, ...) chore_launch(h, s, __FILE__, __LINE__, __VA_ARGS__)
 
+// Workspaces: an operator states its layout ONCE, in a function x_ws(base, shapes...) that carves `base` with a WsCarver and
+// returns the typed pointers and `bytes`: the launcher reads its pointers from it, the exported size function calls it with a
+// null base (only the offsets run).  A braced list is evaluated in order: regions in field order, c.bytes last.  Host only.
+inline size_t ws_align(size_t n) { return (n + 255) & ~(size_t)255; }      // the one spelling of "round up to 256 bytes"
+struct WsCarver {
+    char* base;            // may be null: measure only
+    size_t bytes = 0;      // carved so far
+    explicit WsCarver(void* b) : base((char*)b) {}
+    void pad() { bytes = ws_align(bytes); }
+    template <typename T> T* raw(size_t count) {      // the next `count` elements, nothing after them
+        T* p = base ? (T*)(base + bytes) : nullptr;
+        bytes += count * sizeof(T);
+        return p;
+    }
+    template <typename T> T* take(size_t count) { T* p = raw<T>(count); pad(); return p; }      // ... then up to 256 bytes
+};
+
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using bf16x8 = __attribute__((ext_vector_type(8))) short;  // 8 bf16 in 4 VGPRs

@@ -43,26 +43,25 @@ struct CWs {                    // workspace layout (element offsets, see contac
 };
 
 CWs contact_ws(void* base, int B, int Nh, int No, int P) {
+    const size_t BNh = (size_t)B * Nh, BNo = (size_t)B * No, BP2 = (size_t)B * P * 2;
+    WsCarver c(base);
     CWs w;
-    char* p = (char*)base;
-    size_t off = 0;
-    auto take = [&](size_t n) { char* r = p + off; off += (n + 255) / 256 * 256; return r; };
-    w.label_o = (int*)take(sizeof(int) * B * No);
-    w.sel_h = (int*)take(sizeof(int) * B * Nh);
-    w.sel_o = (int*)take(sizeof(int) * B * No);
-    w.cnt = (int*)take(sizeof(int) * B * 2);
-    w.n_part = (int*)take(sizeof(int) * B * P * 2);
-    w.npairs = (int*)take(sizeof(int));
-    w.nn_h = (int*)take(sizeof(int) * B * Nh);
-    w.nn_o = (int*)take(sizeof(int) * B * No);
-    w.m_h = (float*)take(sizeof(float) * B * Nh);
-    w.m_o = (float*)take(sizeof(float) * B * No);
-    w.pair_sum = (float*)take(sizeof(float) * B * P * 2);
-    w.key_h = (unsigned long long*)take(sizeof(unsigned long long) * B * Nh);
-    w.key_o = (unsigned long long*)take(sizeof(unsigned long long) * B * No);   // contiguous with key_h: one memset
-    w.part_h = (float*)take(sizeof(float) * (size_t)((No + TILE - 1) / TILE) * B * Nh * 3);
-    w.part_o = (float*)take(sizeof(float) * (size_t)((Nh + TILE - 1) / TILE) * B * No * 3);
-    w.bytes = off;
+    w.label_o = c.take<int>(BNo);
+    w.sel_h = c.take<int>(BNh);
+    w.sel_o = c.take<int>(BNo);
+    w.cnt = c.take<int>((size_t)B * 2);
+    w.n_part = c.take<int>(BP2);
+    w.npairs = c.take<int>(1);
+    w.nn_h = c.take<int>(BNh);
+    w.nn_o = c.take<int>(BNo);
+    w.m_h = c.take<float>(BNh);
+    w.m_o = c.take<float>(BNo);
+    w.pair_sum = c.take<float>(BP2);
+    w.key_h = c.take<unsigned long long>(BNh);
+    w.key_o = c.take<unsigned long long>(BNo);   // contiguous with key_h: one memset
+    w.part_h = c.take<float>((size_t)((No + TILE - 1) / TILE) * BNh * 3);
+    w.part_o = c.take<float>((size_t)((Nh + TILE - 1) / TILE) * BNo * 3);
+    w.bytes = c.bytes;
     return w;
 }
 

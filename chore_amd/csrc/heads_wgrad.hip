@@ -403,6 +403,13 @@ __global__ void heads_wgrad_finish_kernel(HeadsWgradArgs a) {
 
 constexpr size_t HW_PART = (size_t)HW_TILES * HW_S * 128 * 128, HW_PART_B = (size_t)HW_TILES * HW_S * 128,
                  HW_PART4 = (size_t)HEAD_NUM * HW_S4 * HW_OMAX * 128, HW_PART_B4 = (size_t)HEAD_NUM * HW_S4 * 16;
+// the workspace: the four tables of partial sums, nothing between them; returns its bytes
+size_t heads_wgrad_ws(HeadsWgradArgs& a, void* base) {
+    WsCarver c(base);
+    a.part = c.raw<float>(HW_PART); a.part_b = c.raw<float>(HW_PART_B);
+    a.part4 = c.raw<float>(HW_PART4); a.part_b4 = c.raw<float>(HW_PART_B4);
+    return c.bytes;
+}
 
 }  // namespace
 
@@ -411,7 +418,7 @@ extern "C" {
 // floats of the gradient arena: per head (df, parts, pca, centers) W1 (128,323) b1 W2 (128,128) b2 W3 b3 W4 (out,128) b4
 size_t chore_heads_wgrad_floats(void) { return head_grad_offset(HEAD_NUM); }
 
-size_t chore_heads_wgrad_workspace_bytes(void) { return (HW_PART + HW_PART_B + HW_PART4 + HW_PART_B4) * sizeof(float); }
+size_t chore_heads_wgrad_workspace_bytes(void) { HeadsWgradArgs a; return heads_wgrad_ws(a, nullptr); }
 
 int chore_heads_wgrad(chore_handle* h, const void* staging, int B, int N, const float* g_df, const float* g_pca,
                       const float* g_parts, const float* g_centers, float* grads, void* workspace, int heads_x3,
@@ -431,10 +438,7 @@ int chore_heads_wgrad(chore_handle* h, const void* staging, int B, int N, const 
     a.dZ = a.H + P * 3 * HEAD_NUM * HEAD_HID;
     a.g[0] = g_df; a.g[1] = g_parts; a.g[2] = g_pca; a.g[3] = g_centers;
     a.B = B; a.N = N;
-    a.part = (float*)workspace;
-    a.part_b = a.part + HW_PART;
-    a.part4 = a.part_b + HW_PART_B;
-    a.part_b4 = a.part4 + HW_PART4;
+    heads_wgrad_ws(a, workspace);
     a.out = grads; a.accumulate = accumulate;
     const size_t smem = (size_t)2 * HW_KT * 256 * sizeof(float);
     if (int rc = heads_x3 ? CHORE_LAUNCH(h, s, heads_wgrad_x3_kernel, dim3(HW_S, HW_TILES), dim3(256), HX_SMEM, a)

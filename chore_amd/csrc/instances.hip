@@ -137,7 +137,8 @@ extern "C" int chore_instances_fwd(chore_handle* h, const float* tri, const int*
         CHORE_FAIL(h, CHORE_EINVAL, "chore_instances_fwd: bad sizes B=%d F=%d size=%d ssaa=%d", B, F, size, ssaa);
     hipStream_t s = (hipStream_t)stream;
     const int S = size * ssaa, nb = rb_bins(S);
-    const RenderWs w = render_ws(workspace, B, F, S);
+    WsCarver c(workspace);
+    const RenderWs w = render_ws(c, B, F, S);
     // the bin counters and the two count outputs = 0 in one grid, no keys; a NULL output has n = 0
     const size_t ncount = (size_t)B * nb * nb, nface = face_samples ? (size_t)B * F : 0, ngroup = group_samples ? (size_t)B * G * 2 : 0;
     const size_t nclear = ncount > nface ? (ncount > ngroup ? ncount : ngroup) : (nface > ngroup ? nface : ngroup);

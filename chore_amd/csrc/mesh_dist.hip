@@ -71,7 +71,6 @@ __host__ __device__ inline int md_chunk_faces(int F, int S) {
     const int ftiles = (F + MD_TILE - 1) / MD_TILE;
     return ((ftiles + S - 1) / S) * MD_TILE;
 }
-inline size_t md_align(size_t x) { return (x + 255) & ~(size_t)255; }
 inline bool md_shape_ok(int B, int N, int V, int F) {
     return B >= 1 && N >= 1 && V >= 1 && F >= 1 && B <= 65535 && (long long)B * N <= (1ll << 30) && (long long)B * F <= (1ll << 26) &&
            (long long)B * V <= (1ll << 28);
@@ -334,6 +333,15 @@ __global__ __launch_bounds__(256) void vertex_kernel(const float* __restrict__ p
     if (i < N) vert_idx[(size_t)b * N + i] = bi;
 }
 
+// workspace of both entry points: Rec [B*F] | keys [S*B*N] | with `wind` also: winding partials float [S*B*N] | RecW [B*F]
+struct MdWs { Rec* rec; unsigned long long* keys; float* wpart; RecW* recw; size_t bytes; };
+MdWs md_ws(void* base, bool wind, int B, int N, int F) {
+    const size_t BF = (size_t)B * F, SBN = (size_t)md_chunks(B, N, F) * B * N;
+    WsCarver c(base);
+    return {c.take<Rec>(BF), c.take<unsigned long long>(SBN), wind ? c.take<float>(SBN) : nullptr,
+            wind ? c.take<RecW>(BF) : nullptr, c.bytes};
+}
+
 // the three launches (+ the nearest-vertex one) of both entry points; `wpart` / `winding` are read by the WIND kernels only
 template <bool WIND>
 int md_run(chore_handle* h, const char* who, const float* points, const float* verts, const int* faces, int B, int N, int V, int F,
@@ -342,28 +350,23 @@ int md_run(chore_handle* h, const char* who, const float* points, const float* v
     if (!points || !verts || !faces || !dist || !workspace || (WIND && !winding)) CHORE_FAIL(h, CHORE_EINVAL, "%s: bad argument", who);
     hipStream_t s = (hipStream_t)stream;
     const int S = md_chunks(B, N, F);
-    Rec* rec = (Rec*)workspace;
-    const size_t key_off = md_align((size_t)B * F * sizeof(Rec));
-    unsigned long long* keys = (unsigned long long*)((char*)workspace + key_off);
-    const size_t w_off = key_off + md_align((size_t)S * B * N * sizeof(unsigned long long));     // where the unsigned workspace ends
-    float* wpart = WIND ? (float*)((char*)workspace + w_off) : nullptr;
-    RecW* recw = WIND ? (RecW*)((char*)workspace + w_off + md_align((size_t)S * B * N * sizeof(float))) : nullptr;
+    const MdWs w = md_ws(workspace, WIND, B, N, F);
     const dim3 grec((F + 255) / 256, B), gdist((N + MD_PTS - 1) / MD_PTS, S, B), gfin((N + 255) / 256, B);
     if constexpr (WIND) {
-        hipLaunchKernelGGL(record_kernel_w, grec, dim3(256), 0, s, verts, faces, V, F, rec, recw);
+        hipLaunchKernelGGL(record_kernel_w, grec, dim3(256), 0, s, verts, faces, V, F, w.rec, w.recw);
         CHORE_LAUNCH_CHECK(h, s);
-        hipLaunchKernelGGL(dist_kernel_w, gdist, dim3(MD_THREADS), 0, s, points, (const Rec*)rec, N, F, md_chunk_faces(F, S), keys,
-                           (const RecW*)recw, wpart);
+        hipLaunchKernelGGL(dist_kernel_w, gdist, dim3(MD_THREADS), 0, s, points, (const Rec*)w.rec, N, F, md_chunk_faces(F, S), w.keys,
+                           (const RecW*)w.recw, w.wpart);
         CHORE_LAUNCH_CHECK(h, s);
-        hipLaunchKernelGGL(finish_kernel_w, gfin, dim3(256), 0, s, points, (const Rec*)rec, (const unsigned long long*)keys, N, F, S, dist,
-                           face_idx, closest, (const float*)wpart, winding);
+        hipLaunchKernelGGL(finish_kernel_w, gfin, dim3(256), 0, s, points, (const Rec*)w.rec, (const unsigned long long*)w.keys, N, F, S, dist,
+                           face_idx, closest, (const float*)w.wpart, winding);
         CHORE_LAUNCH_CHECK(h, s);
     } else {
-        hipLaunchKernelGGL(record_kernel, grec, dim3(256), 0, s, verts, faces, V, F, rec);
+        hipLaunchKernelGGL(record_kernel, grec, dim3(256), 0, s, verts, faces, V, F, w.rec);
         CHORE_LAUNCH_CHECK(h, s);
-        hipLaunchKernelGGL(dist_kernel, gdist, dim3(MD_THREADS), 0, s, points, (const Rec*)rec, N, F, md_chunk_faces(F, S), keys);
+        hipLaunchKernelGGL(dist_kernel, gdist, dim3(MD_THREADS), 0, s, points, (const Rec*)w.rec, N, F, md_chunk_faces(F, S), w.keys);
         CHORE_LAUNCH_CHECK(h, s);
-        hipLaunchKernelGGL(finish_kernel, gfin, dim3(256), 0, s, points, (const Rec*)rec, (const unsigned long long*)keys, N, F, S, dist,
+        hipLaunchKernelGGL(finish_kernel, gfin, dim3(256), 0, s, points, (const Rec*)w.rec, (const unsigned long long*)w.keys, N, F, S, dist,
                            face_idx, closest);
         CHORE_LAUNCH_CHECK(h, s);
     }
@@ -378,11 +381,7 @@ int md_run(chore_handle* h, const char* who, const float* points, const float* v
 
 extern "C" {
 
-size_t chore_mesh_dist_workspace_bytes(int B, int N, int V, int F) {
-    if (!md_shape_ok(B, N, V, F)) return 0;
-    const int S = md_chunks(B, N, F);
-    return md_align((size_t)B * F * sizeof(Rec)) + md_align((size_t)S * B * N * sizeof(unsigned long long));
-}
+size_t chore_mesh_dist_workspace_bytes(int B, int N, int V, int F) { return md_shape_ok(B, N, V, F) ? md_ws(nullptr, false, B, N, F).bytes : 0; }
 
 int chore_mesh_dist_fwd(chore_handle* h, const float* points, const float* verts, const int* faces, int B, int N, int V, int F,
                         float* dist, int* face_idx, float* closest, int* vert_idx, void* workspace, chore_stream_t stream) {
@@ -392,11 +391,7 @@ int chore_mesh_dist_fwd(chore_handle* h, const float* points, const float* verts
 }
 
 // the unsigned call's workspace + one float per (chunk, image, point) + one RecW per (image, face)
-size_t chore_mesh_sdf_workspace_bytes(int B, int N, int V, int F) {
-    const size_t base = chore_mesh_dist_workspace_bytes(B, N, V, F);
-    if (base == 0) return 0;
-    return base + md_align((size_t)md_chunks(B, N, F) * B * N * sizeof(float)) + md_align((size_t)B * F * sizeof(RecW));
-}
+size_t chore_mesh_sdf_workspace_bytes(int B, int N, int V, int F) { return md_shape_ok(B, N, V, F) ? md_ws(nullptr, true, B, N, F).bytes : 0; }
 
 int chore_mesh_sdf_fwd(chore_handle* h, const float* points, const float* verts, const int* faces, int B, int N, int V, int F,
                        float* dist, int* face_idx, float* closest, int* vert_idx, float* winding, void* workspace,

@@ -51,7 +51,6 @@ __host__ __device__ inline int mb_chunk_points(int N, int S) {
     const int ptiles = (N + MB_TILE - 1) / MB_TILE;
     return ((ptiles + S - 1) / S) * MB_TILE;
 }
-inline size_t mb_align(size_t x) { return (x + 255) & ~(size_t)255; }
 inline bool mb_shape_ok(int B, int N, int V, int F) {
     return B >= 1 && N >= 1 && V >= 1 && F >= 1 && B <= 65535 && (long long)B * N <= (1ll << 26) && (long long)B * F <= (1ll << 26) &&
            (long long)B * V <= (1ll << 26);
@@ -181,17 +180,18 @@ __global__ __launch_bounds__(MB_THREADS) void finish_kernel(const float* __restr
     dverts[(size_t)b * V3 + e] = a;
 }
 
+// workspace: one id and one value record per (image, point) | one partial sum per (chunk, image, vertex)
+struct MbWs { RecId* ids; RecVal* vals; float* part; size_t bytes; };
+MbWs mb_ws(void* base, int B, int N, int V) {
+    WsCarver c(base);
+    return {c.take<RecId>((size_t)B * N), c.take<RecVal>((size_t)B * N), c.take<float>((size_t)mb_chunks(B, N, V) * B * V * 3), c.bytes};
+}
+
 }  // namespace
 
 extern "C" {
 
-// one id and one value record per (image, point) + one partial sum per (chunk, image, vertex)
-size_t chore_mesh_dist_bwd_workspace_bytes(int B, int N, int V, int F) {
-    if (!mb_shape_ok(B, N, V, F)) return 0;
-    const int S = mb_chunks(B, N, V);
-    return mb_align((size_t)B * N * sizeof(RecId)) + mb_align((size_t)B * N * sizeof(RecVal)) +
-           mb_align((size_t)S * B * V * 3 * sizeof(float));
-}
+size_t chore_mesh_dist_bwd_workspace_bytes(int B, int N, int V, int F) { return mb_shape_ok(B, N, V, F) ? mb_ws(nullptr, B, N, V).bytes : 0; }
 
 int chore_mesh_dist_bwd(chore_handle* h, const float* points, const float* verts, const int* faces, const int* face_idx,
                         const float* closest, const float* dist, const float* g_dist, int B, int N, int V, int F, float* dpoints,
@@ -202,19 +202,17 @@ int chore_mesh_dist_bwd(chore_handle* h, const float* points, const float* verts
         CHORE_FAIL(h, CHORE_EINVAL, "chore_mesh_dist_bwd: bad argument");
     if (!dpoints && !dverts) return CHORE_OK;
     hipStream_t s = (hipStream_t)stream;
-    RecId* ids = (RecId*)workspace;
-    RecVal* vals = (RecVal*)((char*)workspace + mb_align((size_t)B * N * sizeof(RecId)));
-    float* part = (float*)((char*)vals + mb_align((size_t)B * N * sizeof(RecVal)));
+    const MbWs w = mb_ws(workspace, B, N, V);
     hipLaunchKernelGGL(point_kernel, dim3((N + MB_THREADS - 1) / MB_THREADS, B), dim3(MB_THREADS), 0, s, points, verts, faces, face_idx,
-                       dist, g_dist, N, V, F, dpoints, dverts ? ids : (RecId*)nullptr, dverts ? vals : (RecVal*)nullptr);
+                       dist, g_dist, N, V, F, dpoints, dverts ? w.ids : (RecId*)nullptr, dverts ? w.vals : (RecVal*)nullptr);
     CHORE_LAUNCH_CHECK(h, s);
     if (!dverts) return CHORE_OK;
     const int S = mb_chunks(B, N, V);
-    hipLaunchKernelGGL(gather_kernel, dim3((V + MB_THREADS - 1) / MB_THREADS, S, B), dim3(MB_THREADS), 0, s, (const RecId*)ids,
-                       (const RecVal*)vals, N, V, mb_chunk_points(N, S), S == 1 ? dverts : part);
+    hipLaunchKernelGGL(gather_kernel, dim3((V + MB_THREADS - 1) / MB_THREADS, S, B), dim3(MB_THREADS), 0, s, (const RecId*)w.ids,
+                       (const RecVal*)w.vals, N, V, mb_chunk_points(N, S), S == 1 ? dverts : w.part);
     CHORE_LAUNCH_CHECK(h, s);
     if (S > 1) {
-        hipLaunchKernelGGL(finish_kernel, dim3((V * 3 + MB_THREADS - 1) / MB_THREADS, B), dim3(MB_THREADS), 0, s, (const float*)part, V * 3,
+        hipLaunchKernelGGL(finish_kernel, dim3((V * 3 + MB_THREADS - 1) / MB_THREADS, B), dim3(MB_THREADS), 0, s, (const float*)w.part, V * 3,
                            S, dverts);
         CHORE_LAUNCH_CHECK(h, s);
     }

@@ -79,7 +79,8 @@ extern "C" int chore_render_fwd(chore_handle* h, const float* tri, const float* 
         CHORE_FAIL(h, CHORE_EINVAL, "chore_render_fwd: bad sizes B=%d F=%d ts=%d size=%d ssaa=%d", B, F, ts, size, ssaa);
     hipStream_t s = (hipStream_t)stream;
     const int S = size * ssaa, nb = rb_bins(S);
-    const RenderWs w = render_ws(workspace, B, F, S);
+    WsCarver c(workspace);
+    const RenderWs w = render_ws(c, B, F, S);
     CHORE_HIP_CHECK(h, hipMemsetAsync(w.count, 0, (size_t)B * nb * nb * sizeof(int), s));
     raster_setup(s, tri, B, F, S, w.ts, w.count, w.list);
     CHORE_LAUNCH_CHECK(h, s);

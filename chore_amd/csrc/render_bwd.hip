@@ -21,31 +21,12 @@
 
 namespace {
 
-// workspace: TriSetup [B*F] | colour + alpha float4 [B*S*S] | d rgb + d alpha float4 [B*S*S] | d depth float [B*S*S]
-struct RenderBwdWs {
-    TriSetup* ts;
-    float4* col;
-    float4* grad;
-    float* gdepth;
-};
+// workspace: TriSetup [B*F], padded to 256 bytes | colour + alpha float4 [B*S*S] | d rgb + d alpha float4 [B*S*S] | d depth float [B*S*S]
+struct RenderBwdWs { TriSetup* ts; float4* col; float4* grad; float* gdepth; size_t bytes; };
 inline RenderBwdWs render_bwd_ws(void* workspace, int B, int F, int S) {
     const size_t n = (size_t)B * S * S;
-    char* p = (char*)workspace;
-    RenderBwdWs w;
-    w.ts = (TriSetup*)p;
-    p += rb_align((size_t)B * F * sizeof(TriSetup));
-    w.col = (float4*)p;
-    p += n * sizeof(float4);
-    w.grad = (float4*)p;
-    p += n * sizeof(float4);
-    w.gdepth = (float*)p;
-    return w;
-}
-inline size_t render_bwd_ws_bytes(int B, int F, int ts, int size, int ssaa) {
-    if (ssaa != 1 && ssaa != 2) return 0;
-    if (!render_shape_ok(B, F, ts, size, ssaa)) return 0;
-    const size_t S = (size_t)size * ssaa;
-    return rb_align((size_t)B * F * sizeof(TriSetup)) + (size_t)B * S * S * (2 * sizeof(float4) + sizeof(float));
+    WsCarver c(workspace);
+    return {c.take<TriSetup>((size_t)B * F), c.raw<float4>(n), c.raw<float4>(n), c.raw<float>(n), c.bytes};
 }
 
 // thread = sample (x fastest): its colour and alpha as the forward produced them, and its share of the upstream gradients
@@ -247,7 +228,8 @@ __global__ __launch_bounds__(256) void rbw_gather_kernel(const TriSetup* __restr
 }  // namespace
 
 extern "C" size_t chore_render_bwd_workspace_bytes(int B, int F, int ts, int size, int ssaa) {
-    return render_bwd_ws_bytes(B, F, ts, size, ssaa);
+    if ((ssaa != 1 && ssaa != 2) || !render_shape_ok(B, F, ts, size, ssaa)) return 0;
+    return render_bwd_ws(nullptr, B, F, size * ssaa).bytes;
 }
 
 extern "C" int chore_render_bwd(chore_handle* h, const float* tri, const float* textures, const float* light,

@@ -14,30 +14,22 @@ constexpr int RB_TW = 16, RB_TH = 16; // output pixels per tile; a wave owns an 
 constexpr int RB_CHUNK = 256;        // list entries looked at per pass
 constexpr int RB_TRI_WORDS = 22;     // f[9] + inv[9] + the box: a whole TriSetup
 
-// workspace: TriSetup [B*F] | counters int [B*nb*nb] | lists int [B*nb*nb][F]   (each part padded to 256 bytes)
+// workspace: TriSetup [B*F] | counters int [B*nb*nb] | lists int [B*nb*nb][F]   (the first two padded to 256 bytes; scene.hip carves on)
 struct RenderWs {
     TriSetup* ts;
     int* count;
     int* list;
 };
-__host__ __device__ inline size_t rb_align(size_t x) { return (x + 255) & ~(size_t)255; }
-inline RenderWs render_ws(void* workspace, int B, int F, int S) {
-    const int nb = rb_bins(S);
-    char* p = (char*)workspace;
-    RenderWs w;
-    w.ts = (TriSetup*)p;
-    p += rb_align((size_t)B * F * sizeof(TriSetup));
-    w.count = (int*)p;
-    p += rb_align((size_t)B * nb * nb * sizeof(int));
-    w.list = (int*)p;
-    return w;
+inline RenderWs render_ws(WsCarver& c, int B, int F, int S) {
+    const size_t bins = (size_t)B * rb_bins(S) * rb_bins(S);
+    return {c.take<TriSetup>((size_t)B * F), c.take<int>(bins), c.raw<int>(bins * F)};
 }
 // 0 = unsupported shape
 inline size_t render_ws_bytes(int B, int F, int size, int ssaa) {
     if (B <= 0 || F <= 0 || size <= 0 || (ssaa != 1 && ssaa != 2) || (long long)size * ssaa > 4096) return 0;
-    const int nb = rb_bins(size * ssaa);
-    return rb_align((size_t)B * F * sizeof(TriSetup)) + rb_align((size_t)B * nb * nb * sizeof(int)) +
-           (size_t)B * nb * nb * F * sizeof(int);
+    WsCarver c(nullptr);
+    render_ws(c, B, F, size * ssaa);
+    return c.bytes;
 }
 inline bool render_shape_ok(int B, int F, int ts, int size, int ssaa) {
     return !(B <= 0 || B > 65535 || F <= 0 || ts < 2 || size <= 0 || (long long)size * ssaa > 4096 ||

@@ -194,12 +194,20 @@ __global__ __launch_bounds__(256) void scene_layers_tile_kernel(
     if (sample_id) raster_store_sample_ids<SS>(sample_id, b, px, py, size, id);
 }
 
+// workspace: the render layout, padded to 256 bytes | the splat keys
+struct SceneWs { RenderWs r; unsigned long long* keys; size_t bytes; };
+SceneWs scene_ws(void* base, int B, int F, int size, int ssaa) {
+    WsCarver c(base);
+    const RenderWs r = render_ws(c, B, F, size * ssaa);
+    c.pad();
+    return {r, (unsigned long long*)c.raw<char>(splat_key_bytes(B, size, ssaa)), c.bytes};
+}
+
 }  // namespace
 
 extern "C" size_t chore_scene_workspace_bytes(int B, int F, int N, int size, int ssaa) {
-    const size_t rb = render_ws_bytes(B, F, size, ssaa);
-    if (rb == 0 || !render_shape_ok(B, F, 2, size, ssaa) || !splat_shape_ok(B, N, size, ssaa)) return 0;
-    return rb_align(rb) + splat_key_bytes(B, size, ssaa);
+    if (render_ws_bytes(B, F, size, ssaa) == 0 || !render_shape_ok(B, F, 2, size, ssaa) || !splat_shape_ok(B, N, size, ssaa)) return 0;
+    return scene_ws(nullptr, B, F, size, ssaa).bytes;
 }
 
 // both entry points: the checks, the three shared passes and the tile kernel for `layers` (1 = scene_tile_kernel)
@@ -220,8 +228,9 @@ static int scene_fwd(chore_handle* h, const char* who, const float* tri, const f
         CHORE_FAIL(h, CHORE_EINVAL, "%s: point_depth_bias must be >= 0, got %g", who, (double)point_depth_bias);
     hipStream_t s = (hipStream_t)stream;
     const int S = size * ssaa, nb = rb_bins(S);
-    const RenderWs w = render_ws(workspace, B, F, S);
-    unsigned long long* keys = (unsigned long long*)((char*)workspace + rb_align(render_ws_bytes(B, F, size, ssaa)));
+    const SceneWs sw = scene_ws(workspace, B, F, size, ssaa);
+    const RenderWs& w = sw.r;
+    unsigned long long* keys = sw.keys;
     const size_t nkeys = (size_t)B * S * S, ncount = (size_t)B * nb * nb;
     raster_clear(s, (nkeys + 1) / 2 > ncount ? (nkeys + 1) / 2 : ncount, keys, nkeys, w.count, ncount);
     CHORE_LAUNCH_CHECK(h, s);

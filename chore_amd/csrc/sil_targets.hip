@@ -23,8 +23,6 @@ constexpr int EDT_INF = 1 << 30;         // "no feature in this column"; (x-x')^
 constexpr int EDGE_TILE = 256;           // pixels (= threads) per block of the edge term's forward
 constexpr int EDGE_MAX_K = 31;
 
-inline size_t up256(size_t n) { return (n + 255) / 256 * 256; }
-
 // ---- exact squared distance transform ----------------------------------------------------------------------------------
 // column pass: g2[b,y,x] = (distance to the nearest feature pixel of column x)^2, EDT_INF if the column has none
 __global__ __launch_bounds__(EDT_COL_TILE) void edt_col_kernel(const uint8_t* __restrict__ feat, int H, int W, int* __restrict__ g2) {
@@ -281,6 +279,16 @@ __global__ void edge_bwd_kernel(const float* __restrict__ weight, const int* __r
     g_image[o + p] = __fmul_rn(g[blockIdx.y], __fsub_rn(acc, weight[o + p]));
 }
 
+bool edt_sizes_ok(int B, int H, int W) { return B > 0 && H > 0 && W > 0 && H <= EDT_MAX_DIM && W <= EDT_MAX_DIM && B <= 65535; }
+
+// workspace of chore_sil_edge_edt: feature bytes | column distances | squared distances
+struct EdgeEdtWs { uint8_t* feat; int* g2; int* d2; size_t bytes; };
+EdgeEdtWs edge_edt_ws(void* base, int B, int S) {
+    const size_t n = (size_t)B * S * S;
+    WsCarver c(base);
+    return {c.take<uint8_t>(n), c.take<int>(n), c.take<int>(n), c.bytes};
+}
+
 bool edge_sizes_ok(int B, int S, int ksize) {
     return B > 0 && S > 0 && S <= EDT_MAX_DIM && B <= 65535 && ksize >= 1 && (ksize & 1) && ksize <= EDGE_MAX_K;
 }
@@ -288,15 +296,14 @@ bool edge_sizes_ok(int B, int S, int ksize) {
 }  // namespace
 
 extern "C" size_t chore_edt_workspace_bytes(int B, int H, int W) {
-    if (B <= 0 || H <= 0 || W <= 0 || H > EDT_MAX_DIM || W > EDT_MAX_DIM || B > 65535) return 0;
-    return up256(sizeof(int) * (size_t)B * H * W);
+    return edt_sizes_ok(B, H, W) ? ws_align(sizeof(int) * (size_t)B * H * W) : 0;
 }
 
 extern "C" int chore_edt_sq(chore_handle* h, const uint8_t* feature, int B, int H, int W, int* d2, void* workspace,
                             chore_stream_t stream) {
     CHORE_ENTER(h);
     if (!feature || !d2 || !workspace) CHORE_FAIL(h, CHORE_EINVAL, "chore_edt_sq: null argument");
-    if (B <= 0 || H <= 0 || W <= 0 || H > EDT_MAX_DIM || W > EDT_MAX_DIM || B > 65535)
+    if (!edt_sizes_ok(B, H, W))
         CHORE_FAIL(h, CHORE_EINVAL, "chore_edt_sq: bad sizes B=%d H=%d W=%d (H, W <= %d)", B, H, W, EDT_MAX_DIM);
     hipStream_t s = (hipStream_t)stream;
     edt_launch(feature, B, H, W, (int*)workspace, d2, s);
@@ -321,11 +328,8 @@ extern "C" int chore_edt_tiles(int* col_tile, int* row_tile, int* max_dim) {
     return CHORE_OK;
 }
 
-// workspace of chore_sil_edge_edt: feature bytes, column distances, squared distances
 extern "C" size_t chore_sil_edge_edt_workspace_bytes(int B, int S) {
-    if (B <= 0 || S <= 0 || S > EDT_MAX_DIM || B > 65535) return 0;
-    const size_t n = (size_t)B * S * S;
-    return up256(n) + 2 * up256(sizeof(int) * n);
+    return edt_sizes_ok(B, S, S) ? edge_edt_ws(nullptr, B, S).bytes : 0;
 }
 
 extern "C" int chore_sil_edge_edt(chore_handle* h, const float* image_ref, int B, int S, int ksize, float power, float* edges,
@@ -336,19 +340,17 @@ extern "C" int chore_sil_edge_edt(chore_handle* h, const float* image_ref, int B
         CHORE_FAIL(h, CHORE_EINVAL, "chore_sil_edge_edt: bad sizes B=%d S=%d ksize=%d power=%g", B, S, ksize, (double)power);
     hipStream_t s = (hipStream_t)stream;
     const size_t n = (size_t)B * S * S;
-    uint8_t* feat = (uint8_t*)workspace;
-    int* g2 = (int*)((char*)workspace + up256(n));
-    int* d2 = (int*)((char*)g2 + up256(sizeof(int) * n));
-    hipLaunchKernelGGL(ref_edges_kernel, dim3((S * S + 255) / 256, B), dim3(256), 0, s, image_ref, S, ksize, edges, feat);
-    edt_launch(feat, B, S, S, g2, d2, s);
-    hipLaunchKernelGGL(edt_power_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d2, n, power == 0.25f ? 1 : 0,
+    const EdgeEdtWs w = edge_edt_ws(workspace, B, S);
+    hipLaunchKernelGGL(ref_edges_kernel, dim3((S * S + 255) / 256, B), dim3(256), 0, s, image_ref, S, ksize, edges, w.feat);
+    edt_launch(w.feat, B, S, S, w.g2, w.d2, s);
+    hipLaunchKernelGGL(edt_power_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w.d2, n, power == 0.25f ? 1 : 0,
                        2.0 * (double)power, edt);
     CHORE_LAUNCH_CHECK(h, s);
     return CHORE_OK;
 }
 
 extern "C" size_t chore_sil_targets_workspace_bytes(int B) {
-    return B > 0 ? up256(sizeof(int) * 4 * (size_t)B) : 0;
+    return B > 0 ? ws_align(sizeof(int) * 4 * (size_t)B) : 0;
 }
 
 extern "C" int chore_sil_targets(chore_handle* h, const float* person, const float* obj, const float* crop_centers, int B, int H,
@@ -375,7 +377,7 @@ extern "C" int chore_sil_targets(chore_handle* h, const float* person, const flo
 // one float per block of the forward
 extern "C" size_t chore_sil_edge_workspace_bytes(int B, int S) {
     if (B <= 0 || S <= 0 || S > EDT_MAX_DIM || B > 65535) return 0;
-    return up256(sizeof(float) * (size_t)B * ((S * S + EDGE_TILE - 1) / EDGE_TILE));
+    return ws_align(sizeof(float) * (size_t)B * ((S * S + EDGE_TILE - 1) / EDGE_TILE));
 }
 
 extern "C" int chore_sil_edge_fwd(chore_handle* h, const float* image, const float* weight, int B, int S, int ksize,

@@ -938,11 +938,17 @@ struct WgradPlan {
     int taps, ct;                           // channel tile: ct x ct per workgroup
     int th;                                 // rows of the pixel tile; 0: wgrad128_x3_pc_kernel's run of W128_PX pixels
     int tiles, S;                           // pixel tiles, shares of them
-    size_t share_floats, part_floats;       // one share's partials [Cout/ct][Cin/ct][taps][ct][ct]; all S of them: where part_bias starts
+    size_t share_floats, part_floats;       // one share's partials [Cout/ct][Cin/ct][taps][ct][ct]; all S of them
     size_t ws_bytes;                        // partials and [S][Cout] bias partials
     dim3 grid, block;
     size_t lds;                             // dynamic LDS bytes: the kernel's layout struct
 };
+// the workspace of a plan (S and part_floats set): the partials of all shares | the [S][Cout] bias partials
+struct WgradWs { float *part, *part_bias; size_t bytes; };
+static WgradWs wgrad_ws(void* base, const WgradPlan& p, int Cout) {
+    WsCarver c(base);
+    return {c.raw<float>(p.part_floats), c.raw<float>((size_t)p.S * Cout), c.bytes};
+}
 
 static bool wgrad_use64(int dtype, int taps, int Cin, int Cout) {
     return (dtype == CHORE_BF16 || dtype == CHORE_F16X3) && (taps == 9 || taps == 1) && Cin % 64 == 0 && Cout % 64 == 0;
@@ -988,7 +994,7 @@ static WgradPlan wgrad_describe(int kernel, int elem, int taps, int B, int H, in
     p.S = kernel == WGRAD_K_W32 ? wgrad_shares(B, H, W, Cin, Cout) : wgrad_shares_xcd(p.tiles, pairs);
     p.share_floats = (size_t)pairs * taps * p.ct * p.ct;
     p.part_floats = (size_t)p.S * p.share_floats;
-    p.ws_bytes = (p.part_floats + (size_t)p.S * Cout) * sizeof(float);
+    p.ws_bytes = wgrad_ws(nullptr, p, Cout).bytes;
     p.grid = kernel == WGRAD_K_W32 ? dim3(Cout / CT32, Cin / CT32, p.S) : dim3(p.S * pairs);
     p.block = dim3(kernel == WGRAD_K_W64X3PC || kernel == WGRAD_K_W128X3PC ? 512 : 256);
     p.lds = wgrad_lds_bytes(kernel, elem, taps);
@@ -1152,6 +1158,14 @@ struct GnBwdAcc {                 // exact accumulators, zeroed by the caller
     GroupStat* chan;              // [C]:     sum = dbeta, sq = dgamma
     size_t hc;                    // cells between a low limb and its high limb (the second table, enc_common.h)
 };
+// the accumulators of a (B, C) call in `base`; returns the bytes: grp and chan, and the same again hc cells on (the high limbs)
+static size_t gn_bwd_ws(GnBwdAcc& acc, void* base, int B, int C) {
+    WsCarver c(base);
+    acc.hc = gn_bwd_hi_cells(B, C);
+    acc.grp = c.raw<GroupStat>((size_t)B * GN_GROUPS);
+    acc.chan = c.raw<GroupStat>(C);
+    return acc.hc * sizeof(StatCell) + c.bytes;
+}
 
 template <typename T>
 __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const T* __restrict__ x, const T* __restrict__ da,
@@ -1335,9 +1349,7 @@ int gn_relu_bwd_impl(chore_handle* h, int dtype, const void* x, const void* stat
     if (C % GN_GROUPS || C > 256 || C < 32 || 256 % (C / 4)) CHORE_FAIL(h, CHORE_EINVAL, "chore_gn_relu_bwd: unsupported C=%d", C);
     if (!workspace_zeroed) CHORE_HIP_CHECK(h, hipMemsetAsync(workspace, 0, chore_gn_relu_bwd_workspace_bytes(B, C), s));
     GnBwdAcc acc;
-    acc.grp = (GroupStat*)workspace;
-    acc.chan = acc.grp + (size_t)B * GN_GROUPS;
-    acc.hc = gn_bwd_hi_cells(B, C);
+    gn_bwd_ws(acc, workspace, B, C);
     int S = HW / 128;          // pixels per share: 128 measured a little faster than 64 / 256 on the training step
     if (S < 1) S = 1;
     if (S > GN_SPLITS_MAX) S = GN_SPLITS_MAX;
@@ -1377,8 +1389,9 @@ int conv2d_bwd_weight_impl(chore_handle* h, int dtype, int taps, const void* x, 
     a.x = x; a.st = (const GroupStat*)stats; a.gamma = gamma; a.beta = beta; a.dy = dy;
     a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
     a.xs = Cin; a.ys = dy_stride; a.npix = (long long)B * H * W;
-    a.part = (float*)workspace;
-    a.part_bias = dbias ? a.part + p.part_floats : nullptr;
+    const WgradWs w = wgrad_ws(workspace, p, Cout);
+    a.part = w.part;
+    a.part_bias = dbias ? w.part_bias : nullptr;
     a.S = p.S;
     // the witness of this launch (chore_debug_last_wgrad; host stores only)
     chore_note_wgrad(h, p.kernel, p.elem, taps, p.ct, p.S, p.tiles,
@@ -1499,7 +1512,7 @@ int chore_stem_bwd_weight(chore_handle* h, int dtype, const float* images, int B
     return CHORE_OK;
 }
 
-size_t chore_gn_relu_bwd_workspace_bytes(int B, int C) { return (gn_bwd_hi_cells(B, C) + ((size_t)B * GN_GROUPS + C) * 2) * sizeof(StatCell); }
+size_t chore_gn_relu_bwd_workspace_bytes(int B, int C) { GnBwdAcc acc; return gn_bwd_ws(acc, nullptr, B, C); }
 
 // da = gradient w.r.t. relu(groupnorm(x)) -> dx, dgamma (C), dbeta (C)
 int chore_gn_relu_bwd(chore_handle* h, int dtype, const void* x, const void* stats, const float* gamma, const float* beta,
