@@ -31,6 +31,17 @@ bool make_dims(Dims& d, int dtype, int B, int H, int W, int Cin, int Cout) {
     d.down = Cin != Cout;
     return true;
 }
+// What the block's launches accept of a shape make_dims lets through: every GroupNorm(32, C) of the block -- over Cin (bn1, bn4),
+// Cout/2, Cout/4 and the statistics of y over Cout -- needs a group size of 1, 2, 4 or 8.  Cout in {128, 256} always has one;
+// Cin = 96, 160, 192, 224 has not.  Both entry points ask BEFORE their first launch: the launches refuse such a Cin themselves,
+// but in the backward only the last GroupNorm backward does, after weight-gradient kernels went onto the side stream -- the call
+// then returned without the join, with kernels still writing the caller's workspace.  (The size functions keep answering
+// for every shape make_dims accepts.)  -> the offending channel count, 0: fine
+int bad_group_channels(const Dims& d) {
+    for (int c : {d.Cin, d.Cout, d.C1, d.C2})
+        if (!conv_gn_group_ok(c)) return c;
+    return 0;
+}
 
 // saved (forward -> backward): statistics [x | o1 | o2 | y], then o1, o2
 struct Saved {
@@ -135,6 +146,9 @@ int chore_convblock_fwd(chore_handle* h, int dtype, const void* x, const void* x
     CHORE_ENTER(h);
     Dims d;
     if (!make_dims(d, dtype, B, H, W, Cin, Cout)) CHORE_FAIL(h, CHORE_EINVAL, "chore_convblock_fwd: unsupported shape Cin=%d Cout=%d", Cin, Cout);
+    if (const int c = bad_group_channels(d))
+        CHORE_FAIL(h, CHORE_EINVAL, "chore_convblock_fwd: GroupNorm over %d channels unsupported (group size must be 1, 2, 4 or 8; Cin=%d Cout=%d)", c, Cin, Cout);
+    if (d.down && !wd) CHORE_FAIL(h, CHORE_EINVAL, "chore_convblock_fwd: Cin=%d != Cout=%d needs the downsample weight wd", Cin, Cout);
     if (!x || !w1 || !w2 || !w3 || !gb || !y || !saved || !workspace || (d.down && !wd))
         CHORE_FAIL(h, CHORE_EINVAL, "chore_convblock_fwd: null argument");
     hipStream_t s = (hipStream_t)stream;
@@ -207,6 +221,9 @@ int chore_convblock_bwd(chore_handle* h, int dtype, const void* x, const void* x
     CHORE_ENTER(h);
     Dims d;
     if (!make_dims(d, dtype, B, H, W, Cin, Cout)) CHORE_FAIL(h, CHORE_EINVAL, "chore_convblock_bwd: unsupported shape Cin=%d Cout=%d", Cin, Cout);
+    if (const int c = bad_group_channels(d))
+        CHORE_FAIL(h, CHORE_EINVAL, "chore_convblock_bwd: GroupNorm over %d channels unsupported (group size must be 1, 2, 4 or 8; Cin=%d Cout=%d)", c, Cin, Cout);
+    if (d.down && !wd) CHORE_FAIL(h, CHORE_EINVAL, "chore_convblock_bwd: Cin=%d != Cout=%d needs the downsample weight wd", Cin, Cout);
     if (!x || !dy || !w1 || !w2 || !w3 || !gb || !saved || !dx || !grads || !workspace || (d.down && !wd))
         CHORE_FAIL(h, CHORE_EINVAL, "chore_convblock_bwd: null argument");
     hipStream_t s = (hipStream_t)stream;

@@ -1158,6 +1158,23 @@ struct GnBwdAcc {                 // exact accumulators, zeroed by the caller
     GroupStat* chan;              // [C]:     sum = dbeta, sq = dgamma
     size_t hc;                    // cells between a low limb and its high limb (the second table, enc_common.h)
 };
+// These cells hold sums of GRADIENTS, which have any magnitude, where the activation statistics hold sums of O(1) values: with the
+// statistics' unit of 2^-40 every add dropped up to 9e-13, so dgamma / dbeta of a layer whose upstream gradient is 2e-11 (a slice of dy
+// at 2^-12 of a 1e-7 maximum) came out 5e-3 wrong, in every mode.  The same two-limb cells with the unit 2^-56: a drop of 1.4e-17 per
+// add, totals up to 2^39.  (lo is in [0, 2^32), hi = floor(x 2^24): |x| < 2^39 for the conversion.)
+__device__ __forceinline__ void grad_add(StatCell* c, size_t hi_cells, float x) {
+    const double d = (double)x * 0x1p56;
+    const double h = floor(d * 0x1p-32);
+    const long long hi = (long long)h;
+    const unsigned long long lo = (unsigned long long)(d - h * 0x1p32);
+    (void)__hip_atomic_fetch_add(&c->lo, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (hi != 0) (void)__hip_atomic_fetch_add(&c[hi_cells].hi, hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ double grad_read(const StatCell* c, size_t hi_cells) {
+    const unsigned long long lo = c->lo;
+    const long long top = c[hi_cells].hi + (long long)(lo >> 32);
+    return ((double)top * 0x1p32 + (double)(lo & 0xffffffffull)) * 0x1p-56;
+}
 // the accumulators of a (B, C) call in `base`; returns the bytes: grp and chan, and the same again hc cells on (the high limbs)
 static size_t gn_bwd_ws(GnBwdAcc& acc, void* base, int B, int C) {
     WsCarver c(base);
@@ -1242,12 +1259,12 @@ __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const T* __restrict_
         for (int i = 0; i < P; ++i)
 #pragma unroll
             for (int k = 0; k < 4; ++k) t[k] += red[k][i * C + tid];
-        stat_add(&acc.chan[tid].sum, acc.hc, t[0]);
-        stat_add(&acc.chan[tid].sq, acc.hc, t[1]);
+        grad_add(&acc.chan[tid].sum, acc.hc, t[0]);
+        grad_add(&acc.chan[tid].sq, acc.hc, t[1]);
         const float g1 = group_lane_sum(t[2], gs), g2 = group_lane_sum(t[3], gs);
         GroupStat* o = acc.grp + (size_t)b * GN_GROUPS + tid / gs;      // two lanes of the group, concurrently
-        if (tid % gs == 0) stat_add(&o->sum, acc.hc, g1);
-        if (tid % gs == (gs > 1 ? 1 : 0)) stat_add(&o->sq, acc.hc, g2);
+        if (tid % gs == 0) grad_add(&o->sum, acc.hc, g1);
+        if (tid % gs == (gs > 1 ? 1 : 0)) grad_add(&o->sq, acc.hc, g2);
     }
 }
 
@@ -1277,13 +1294,13 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const T* __restrict__
         pc[7 * tid] = (float)mean;
         pc[7 * tid + 1] = rstd;
         pc[7 * tid + 2] = gamma[tid];
-        pc[7 * tid + 3] = (float)(stat_read(&ga->sum, acc.hc) / n);
-        pc[7 * tid + 4] = (float)(stat_read(&ga->sq, acc.hc) / n);
+        pc[7 * tid + 3] = (float)(grad_read(&ga->sum, acc.hc) / n);
+        pc[7 * tid + 4] = (float)(grad_read(&ga->sq, acc.hc) / n);
         pc[7 * tid + 5] = scale;
         pc[7 * tid + 6] = beta[tid] - (float)mean * scale;
         if (blockIdx.x == 0 && b == 0) {     // the parameter gradients: totals over the whole batch
-            dbeta[tid] = (float)stat_read(&acc.chan[tid].sum, acc.hc);
-            dgamma[tid] = (float)stat_read(&acc.chan[tid].sq, acc.hc);
+            dbeta[tid] = (float)grad_read(&acc.chan[tid].sum, acc.hc);
+            dgamma[tid] = (float)grad_read(&acc.chan[tid].sq, acc.hc);
         }
     }
     __syncthreads();

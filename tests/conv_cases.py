@@ -161,7 +161,8 @@ def _coverage():
             t[("rw", dt, cin, cout, "")] = None
             t[("rw", dt, cin, cout, "res")] = "a residual reaches conv_rw_kernel only from the encoder program (test_encoder_512_checksums)"
     t[("rw", "x3s", 256, 256, "")] = None
-    t[("rw", "x3s", 256, 256, "res")] = "the residual form of the scaled data gradient exists only inside chore_convblock_bwd"
+    t[("rw", "x3s", 256, 256, "res")] = ("instantiated, but no caller launches it: no data gradient carries a residual, and the ConvBlock operator's only "
+                                         "1x1 data gradient has Cin != Cout (tests/test_convblock_coverage_table.py holds both)")
     for dt, dflt in SMALL_DEFAULT_ROWS.items():
         for cin in (64, 128, 256):
             for rows in SMALL_ROWS:

@@ -114,8 +114,8 @@ def _coverage():
     t[("w32", "fp32", 1, "gemm_tn")] = ("chore_gemm_tn_f32 is no convolution layer: test_gpu_bwd_operators.py::test_gemm_tn calls it against "
                                         "float64 and asserts this record of the witness itself")
     t[("any", "any", 0, "strided dy, deferred finish")] = (
-        "out of scope: a channel-strided dy and wgrad_finish_multi_kernel exist only inside chore_convblock_bwd, which "
-        "test_conv_block_operator_equals_layerwise_composition holds bit-equal to the per-layer composition checked here")
+        "not through chore_conv2d_bwd_weight: a channel-strided dy and wgrad_finish_multi_kernel exist only inside chore_convblock_bwd; "
+        "tests/test_gpu_convblock_kernels.py compares all five kernels under them with float64 (tests/test_convblock_coverage_table.py)")
     return t
 
 
