@@ -212,6 +212,10 @@ SIGNATURES = {
     "chore_sil_edge_workspace_bytes": (c_size_t, [c_int, c_int]),
     "chore_sil_edge_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "chore_sil_edge_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "chore_sil_depth": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
+    "chore_ordinal_depth_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "chore_ordinal_depth_fwd": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, c_float, c_float] + [c_void_p] * 5),
+    "chore_ordinal_depth_bwd": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_void_p, c_void_p]),
     "chore_render_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "chore_render_fwd": (c_int, [c_void_p] * 4 + [c_int] * 5 + [c_float] * 3 + [c_void_p] * 7),
     "chore_render_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),

@@ -140,6 +140,68 @@ __device__ __forceinline__ bool raster_hit(const float* f, const float* m, float
     return !(zp <= near || far <= zp);
 }
 
+// ---- the backward of the depth map (rasterize_cuda_kernel.cu:588-638), shared by render_bwd.hip's gather and ordinal_depth.hip.
+// A sample the face won, with its weights w and depth zp, and the upstream gradient g of that depth: A_k += g zp^2 w_k
+__device__ __forceinline__ void raster_depth_bwd_sample(float g, const float* w, float zp, float* A) {
+    const float a = g * (zp * zp);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) A[k] += a * w[k];
+}
+// the face's nine components from its three sums: d z_k = A_k / z_k^2, d (x, y)_k = -tmp_l A_k S / 2, tmp_l = sum_m -inv[3 m + l] / z_m
+__device__ __forceinline__ void raster_depth_bwd_face(const TriSetup& t, const float* A, int S, float* g9) {
+    float tmp[2] = {0.f, 0.f};
+#pragma unroll
+    for (int l = 0; l < 2; ++l)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) tmp[l] += -t.inv[3 * k + l] / t.f[3 * k + 2];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        // a == 0: no sample of this triangle carries a depth gradient (a zero-area triangle has no finite inverse)
+        const float a = A[k], z = t.f[3 * k + 2];
+        g9[3 * k + 2] = a == 0.f ? 0.f : a / (z * z);
+#pragma unroll
+        for (int l = 0; l < 2; ++l) g9[3 * k + l] = a == 0.f ? 0.f : -a * tmp[l] * (float)S / 2.f;
+    }
+}
+// The pixels a face won, walked by its 256-thread workgroup: the aligned 16 x 16 tiles that the face's box meets (exactly where the
+// forward tested it), tiles in row-major order, thread = one pixel of a tile.  fn(q, x, y, w, zp) for every pixel (x, y) of the
+// S x S winner map `fim` (ONE image) whose winner is `face`: q = y * S + x, w and zp its weights and depth rebuilt with the
+// forward's expressions.  Returns whether this THREAD met one.  The box must not be empty (x0 <= x1, y0 <= y1).
+template <class Fn>
+__device__ __forceinline__ int raster_for_each_won_pixel(const TriSetup& t, const int* __restrict__ fim, int face, int S, Fn&& fn) {
+    const int bx0 = t.x0 & ~15, bx1 = min(t.x1 | 15, S - 1), by0 = t.y0 & ~15, by1 = min(t.y1 | 15, S - 1);
+    const int lx = threadIdx.x & 15, ly = threadIdx.x >> 4;
+    int mine = 0;
+    for (int ty = by0; ty <= by1; ty += 16)
+        for (int tx = bx0; tx <= bx1; tx += 16) {
+            const int x = tx + lx, y = ty + ly;
+            if (x > bx1 || y > by1) continue;
+            const size_t q = (size_t)y * S + x;
+            if (fim[q] != face) continue;
+            mine = 1;
+            float w[3], zp;
+            raster_weights(t.f, t.inv, (float)x, (float)y, w, zp);
+            fn(q, x, y, w, zp);
+        }
+    return mine;
+}
+// The sums of a 256-thread workgroup over N per-thread values: a fixed butterfly per wave, then the four waves in order.  Every
+// thread calls it; red[0][k] holds sum k afterwards, for every thread (both barriers are inside).
+template <int N>
+__device__ __forceinline__ void raster_wg_sum(const float* acc, float (*red)[N]) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        float v = acc[k];
+#pragma unroll
+        for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+        if (lane == 0) red[wave][k] = v;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < N) red[0][threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+    __syncthreads();
+}
+
 // ---- the backward of the pixel map (rasterize_cuda_kernel.cu:290-549): the edge walk, shared by silhouette.hip (alpha
 // alone) and render_bwd.hip (alpha + rgb).  An image type Im says what a pixel holds and what it contributes:
 //   int size;  size_t at(axis, d0, d1): the pixel with coordinate d0 along the walk axis and d1 across it;

@@ -112,16 +112,13 @@ __global__ __launch_bounds__(256) void rbw_gather_kernel(const TriSetup* __restr
     __shared__ TriSetup tsh;
     const int i = blockIdx.x;
     const int b = i / F, fn = i - b * F;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x;
     if (tid < RB_TRI_WORDS) reinterpret_cast<int*>(&tsh)[tid] = reinterpret_cast<const int*>(ts + i)[tid];
     __syncthreads();
     const TriSetup& t = tsh;
     const int nt3 = tsz * tsz * tsz;
     const bool empty = t.x0 > t.x1 || t.y0 > t.y1;      // culled or out of view: it won no sample
     const int passes = (do_rgb && grad_textures) ? (nt3 + RBW_TEXELS - 1) / RBW_TEXELS : 1;
-    // the forward tested this triangle on every aligned 16 x 16 tile its box meets
-    const int bx0 = t.x0 & ~15, bx1 = min(t.x1 | 15, S - 1), by0 = t.y0 & ~15, by1 = min(t.y1 | 15, S - 1);
-    const int lx = tid & 15, ly = tid >> 4;
     const size_t img = (size_t)b * S * S;
     const float tmax = (float)(tsz - 1) - tex_eps;
     float lt[3] = {1.f, 1.f, 1.f};
@@ -139,80 +136,48 @@ __global__ __launch_bounds__(256) void rbw_gather_kernel(const TriSetup* __restr
 
     for (int pass = 0; pass < passes; ++pass) {
         float acc[RBW_NACC];
-        int mine = 0;
 #pragma unroll
         for (int k = 0; k < RBW_NACC; ++k) acc[k] = 0.f;
-        for (int ty = by0; ty <= by1; ty += 16)
-            for (int tx = bx0; tx <= bx1; tx += 16) {
-                const int x = tx + lx, y = ty + ly;
-                if (x > bx1 || y > by1) continue;
-                const size_t q = img + (size_t)y * S + x;
-                if (fim[q] != fn) continue;
-                mine = 1;
-                float w[3], zp;
-                raster_weights(t.f, t.inv, (float)x, (float)y, w, zp);
-                if (pass == 0) {
-                    const float a = gdepth[q] * (zp * zp);
+        // the forward tested this triangle on every aligned 16 x 16 tile its box meets: raster_for_each_won_pixel walks those
+        const int mine = raster_for_each_won_pixel(t, fim + img, fn, S, [&](size_t p, int, int, const float* w, float zp) {
+            const size_t q = img + p;
+            if (pass == 0) raster_depth_bwd_sample(gdepth[q], w, zp, acc);
+            if (!do_rgb) return;
+            const float4 g4 = grad[q];
+            const float g[3] = {g4.x, g4.y, g4.z};
+            float fr[3];
+            int ti[3];
+            rb_tex_pos(t.f, w, zp, tsz, tmax, ti, fr);      // the forward's sampling position: rb_shade calls the same
+            if (pass == 0 && grad_light) {       // d light = d rgb x the blended texel
+                float c[3];
+                rb_tex_blend(tex, tsz, ti, fr, c);
 #pragma unroll
-                    for (int k = 0; k < 3; ++k) acc[k] += a * w[k];
-                }
-                if (!do_rgb) continue;
-                const float4 g4 = grad[q];
-                const float g[3] = {g4.x, g4.y, g4.z};
-                float fr[3];
-                int ti[3];
-                rb_tex_pos(t.f, w, zp, tsz, tmax, ti, fr);      // the forward's sampling position: rb_shade calls the same
-                if (pass == 0 && grad_light) {       // d light = d rgb x the blended texel
-                    float c[3];
-                    rb_tex_blend(tex, tsz, ti, fr, c);
+                for (int k = 0; k < 3; ++k) acc[3 + k] += g[k] * c[k];
+            }
+            if (grad_textures) {
+                const float gl[3] = {g[0] * lt[0], g[1] * lt[1], g[2] * lt[2]};
 #pragma unroll
-                    for (int k = 0; k < 3; ++k) acc[3 + k] += g[k] * c[k];
-                }
-                if (grad_textures) {
-                    const float gl[3] = {g[0] * lt[0], g[1] * lt[1], g[2] * lt[2]};
+                for (int u = 0; u < RBW_TEXELS; ++u) {
+                    const int lin = pass * RBW_TEXELS + u;           // texel (i0, i1, i2), uniform
+                    const int i0 = lin / (tsz * tsz), i1 = (lin / tsz) % tsz, i2 = lin % tsz;
+                    const int id[3] = {i0, i1, i2};
+                    float wt = 1.f;
 #pragma unroll
-                    for (int u = 0; u < RBW_TEXELS; ++u) {
-                        const int lin = pass * RBW_TEXELS + u;           // texel (i0, i1, i2), uniform
-                        const int i0 = lin / (tsz * tsz), i1 = (lin / tsz) % tsz, i2 = lin % tsz;
-                        const int id[3] = {i0, i1, i2};
-                        float wt = 1.f;
+                    for (int k = 0; k < 3; ++k)      // the weight of index id[k] along axis k: lower + upper tap
+                        wt *= (id[k] == ti[k] ? 1.f - fr[k] : 0.f) + (id[k] == min(ti[k] + 1, tsz - 1) ? fr[k] : 0.f);
 #pragma unroll
-                        for (int k = 0; k < 3; ++k)      // the weight of index id[k] along axis k: lower + upper tap
-                            wt *= (id[k] == ti[k] ? 1.f - fr[k] : 0.f) + (id[k] == min(ti[k] + 1, tsz - 1) ? fr[k] : 0.f);
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) acc[6 + 3 * u + k] += wt * gl[k];
-                    }
+                    for (int k = 0; k < 3; ++k) acc[6 + 3 * u + k] += wt * gl[k];
                 }
             }
+        });
         // most triangles of a fine mesh win no sample (hidden, or between the sample centres)
         if (!__syncthreads_or(mine)) { nothing(); return; }
         // the workgroup's sums: a fixed butterfly per wave, then the four waves in order
-#pragma unroll
-        for (int k = 0; k < RBW_NACC; ++k) {
-            float v = acc[k];
-#pragma unroll
-            for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-            if (lane == 0) red[wave][k] = v;
-        }
-        __syncthreads();
-        if (tid < RBW_NACC) red[0][tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
-        __syncthreads();
+        raster_wg_sum<RBW_NACC>(acc, red);
         if (pass == 0 && tid == 0) {
-            // backward_depth_map: d z_k = A_k / z_k^2, d (x, y)_k = -tmp_l A_k S / 2 with A_k = sum d depth * w_k * depth^2
+            // backward_depth_map, with A_k = sum d depth * w_k * depth^2 in red[0][0..2]
             float g9[9];
-            float tmp[2] = {0.f, 0.f};
-#pragma unroll
-            for (int l = 0; l < 2; ++l)
-#pragma unroll
-                for (int k = 0; k < 3; ++k) tmp[l] += -t.inv[3 * k + l] / t.f[3 * k + 2];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                // a == 0: no sample of this triangle carries a depth gradient (a zero-area triangle has no finite inverse)
-                const float a = red[0][k], z = t.f[3 * k + 2];
-                g9[3 * k + 2] = a == 0.f ? 0.f : a / (z * z);
-#pragma unroll
-                for (int l = 0; l < 2; ++l) g9[3 * k + l] = a == 0.f ? 0.f : -a * tmp[l] * (float)S / 2.f;
-            }
+            raster_depth_bwd_face(t, red[0], S, g9);
             float* out = grad_tri + (size_t)i * 9;
 #pragma unroll
             for (int k = 0; k < 9; ++k) out[k] = accumulate ? out[k] + g9[k] : g9[k];

@@ -20,6 +20,11 @@ that already own the cropped masks can pass them with `SilLossROI.from_crops`.
 `SilLossROI.from_masks` / `set_masks` do the constructor's work on the device without a host round trip (csrc/sil_targets.hip:
 chore_sil_targets, chore_sil_edge_edt), so a kept fitting chain refreshes its term inside recorded graphs; `edge_loss` is
 PHOSA's edge term on `edt_ref_edge` (chore_sil_edge_fwd / _bwd), an opt-in term of the 'sil' phase that the reference does not have.
+
+`set_occluder` / `depth_loss` are PHOSA's ordinal depth term (csrc/ordinal_depth.hip), opt-in as well: the body's depth image over
+the ROI cameras is a constant of the call (the body is not stepped, it gets no gradient), the object's depth comes from the
+winner map the mask term computes anyway (`mask_loss(parts=True)`).  A pixel the crops label as person AND object counts as
+object, as for the mask term (cvt_masks) -- PHOSA's `mask_i & ~mask_j` would drop it from the object's side too.
 """
 import os
 
@@ -136,6 +141,58 @@ class _EdgeTermFn(torch.autograd.Function):
         _lib.check(_lib.lib.chore_sil_edge_bwd(h, w.data_ptr(), arg.data_ptr(), g.data_ptr(), B, S, ctx.ksize, gi.data_ptr(),
                                                torch.cuda.current_stream(dev).cuda_stream), h, "chore_sil_edge_bwd")
         return gi, None, None
+
+
+DEPTH_CLAMP = 2.0       # PHOSA's clamp of the depth difference in the ordinal depth term
+
+
+def ordinal_depth_counts(tri, face_index, occ_depth, image_ref, keep_mask, c=DEPTH_CLAMP):
+    """chore_ordinal_depth_fwd on device tensors: (per-frame sums (B), coef (B,S,S), counts (B,4) int32: pixels in case A, in
+    case B, in person-and-both, in object-and-both), then the contiguous float triangles and winner map it read.  No gradient; _OrdinalDepthFn and the depth-order report call it."""
+    if not tri.is_cuda:
+        raise RuntimeError("chore_amd needs device tensors (no CPU path)")
+    dev = tri.device
+    h = _lib.handle(dev.index or 0)
+    t = tri.detach().float().contiguous()
+    B, Fn = t.shape[:2]
+    S = face_index.shape[1]
+    fim = face_index.contiguous()
+    maps = [m.detach().float().contiguous() for m in (occ_depth, image_ref, keep_mask)]
+    if tuple(face_index.shape) != (B, S, S) or face_index.dtype != torch.int32 or any(tuple(m.shape) != (B, S, S) for m in maps):
+        raise ValueError("ordinal depth term: (B,S,S) int32 face_index and (B,S,S) occluder depth and masks expected")
+    sums = torch.empty(B, dtype=torch.float32, device=dev)
+    coef = torch.empty(B, S, S, dtype=torch.float32, device=dev)
+    counts = torch.empty(B, 4, dtype=torch.int32, device=dev)
+    ws = torch.empty(max(_lib.lib.chore_ordinal_depth_workspace_bytes(B, S), 1), dtype=torch.uint8, device=dev)
+    _lib.check(_lib.lib.chore_ordinal_depth_fwd(h, t.data_ptr(), fim.data_ptr(), maps[0].data_ptr(),
+                                                maps[1].data_ptr(), maps[2].data_ptr(), B, Fn, S, FAR, float(c), sums.data_ptr(),
+                                                coef.data_ptr(), counts.data_ptr(), ws.data_ptr(),
+                                                torch.cuda.current_stream(dev).cuda_stream), h, "chore_ordinal_depth_fwd")
+    return sums, coef, counts, t, fim
+
+
+class _OrdinalDepthFn(torch.autograd.Function):
+    """tri (B,F,3,3) and the step's winner map -> (B) sums of the ordinal depth term against the constant occluder depth;
+    gradient for the triangles only (it feeds _PlacedTrianglesFn's backward; the occluder and the masks get none)"""
+
+    @staticmethod
+    def forward(ctx, tri, face_index, occ_depth, image_ref, keep_mask, c):
+        sums, coef, _, t, fim = ordinal_depth_counts(tri, face_index, occ_depth, image_ref, keep_mask, c)
+        ctx.save_for_backward(t, fim, coef)
+        return sums
+
+    @staticmethod
+    def backward(ctx, g):
+        t, fim, coef = ctx.saved_tensors
+        dev = t.device
+        h = _lib.handle(dev.index or 0)
+        B, Fn = t.shape[:2]
+        g = g.float().contiguous()
+        gt = torch.empty_like(t)
+        _lib.check(_lib.lib.chore_ordinal_depth_bwd(h, t.data_ptr(), fim.data_ptr(), coef.data_ptr(), g.data_ptr(), B, Fn,
+                                                    fim.shape[1], gt.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), h,
+                   "chore_ordinal_depth_bwd")
+        return gt, None, None, None, None, None
 
 
 def corner_adjacency(faces, num_verts):
@@ -342,7 +399,10 @@ class SilLossROI(nn.Module):
         """take over another instance's per-image data IN PLACE (reference and keep masks, ROI cameras, edge distance
         transform): a recorded fitting step keeps reading this object's buffers across loader batches
         (recon_fit_behave._FitSlot); the template (vertices, faces, corner lists) does not change"""
-        for name in ("image_ref", "keep_mask", "K", "edt_ref_edge"):
+        names = ("image_ref", "keep_mask", "K", "edt_ref_edge")
+        if hasattr(self, "occ_depth") and hasattr(other, "occ_depth"):       # the occluder of the ordinal depth term, when both have one
+            names += ("occ_depth",)
+        for name in names:
             mine, theirs = getattr(self, name), getattr(other, name)
             if mine.shape != theirs.shape:
                 raise ValueError("SilLossROI.load_from: %s has another shape" % name)
@@ -393,20 +453,91 @@ class SilLossROI(nn.Module):
         verts = torch.bmm(self.vertices, R) + obj_t.unsqueeze(1)
         return obj_s.view(-1, 1, 1) * verts
 
+    def render_parts(self, R, obj_t, obj_s):
+        """what one placement and one rasterisation of the step give: (silhouettes (B,S,S) as render() returns them, the
+        (B,2F,3,3) triangle list, the (B,S,S) int32 winner map of chore_silhouette_fwd, rows NOT flipped).  The mask term and
+        the ordinal depth term of a step share them.  Device path only."""
+        if not (R.is_cuda and self.vertices.is_cuda and tuple(obj_s.shape) == (self.vertices.shape[0],)):
+            raise RuntimeError("SilLossROI.render_parts needs device tensors and one scale per frame (no CPU path)")
+        tri = _PlacedTrianglesFn.apply(R, obj_t, obj_s, self.vertices, self.faces32, self.K, self.R, self.t, self.adj_off, self.adj)
+        alpha, fim = _RasterizeFn.apply(tri, self.rend_size)
+        return alpha.flip(1), tri, fim
+
     def render(self, R, obj_t, obj_s):
         """silhouettes (B,S,S) of the template under the pose: apply_transformation -> render_silhouettes"""
         if (not os.environ.get("CHORE_SIL_TORCH_PROJECT") and R.is_cuda and self.vertices.is_cuda and
                 tuple(obj_s.shape) == (self.vertices.shape[0],)):
-            tri = _PlacedTrianglesFn.apply(R, obj_t, obj_s, self.vertices, self.faces32, self.K, self.R, self.t, self.adj_off, self.adj)
-            alpha, _ = _RasterizeFn.apply(tri, self.rend_size)
-            return alpha.flip(1)
+            return self.render_parts(R, obj_t, obj_s)[0]
         verts = self.apply_transformation(R, obj_t, obj_s)
         return render_silhouettes(verts, self.faces, self.K, self.R, self.t, self.rend_size)
 
-    def mask_loss(self, R, obj_t, obj_s):
-        """forward()[0] without the outputs the fitting loop does not read (the edge image costs a max-pool per step)"""
-        image = self.keep_mask * self.render(R, obj_t, obj_s)
-        return {"mask": torch.sum((image - self.image_ref) ** 2, dim=(1, 2)).mean()}, image
+    def mask_loss(self, R, obj_t, obj_s, parts=False):
+        """forward()[0] without the outputs the fitting loop does not read (the edge image costs a max-pool per step).
+        parts: also the step's triangle list and winner map (render_parts), for depth_loss: ({"mask": ...}, image, tri, face_index)"""
+        if parts:
+            rendered, tri, fim = self.render_parts(R, obj_t, obj_s)
+        else:
+            rendered = self.render(R, obj_t, obj_s)
+        image = self.keep_mask * rendered
+        loss = {"mask": torch.sum((image - self.image_ref) ** 2, dim=(1, 2)).mean()}
+        return (loss, image, tri, fim) if parts else (loss, image)
+
+    @torch.no_grad()
+    def set_occluder(self, verts, faces):
+        """the constant occluder of the ordinal depth term: (B,V,3) camera-space vertices (the body; they are placed with the
+        identity pose, both windings) and an (F,3) face array -> the kept buffer `occ_depth` (B,S,S): the depth of the nearest
+        face at every pixel of this term's ROI cameras, FAR where there is none, in the orientation of image_ref
+        (chore_sil_project_fwd, chore_silhouette_fwd, chore_sil_depth).  Refreshed IN PLACE on later calls (a recorded step keeps
+        reading the buffer); no host synchronisation.  The occluder gets no gradient: the object fit does not step the body."""
+        dev = self.image_ref.device
+        B, S = self.image_ref.shape[:2]
+        v = torch.as_tensor(verts).detach().to(device=dev, dtype=torch.float32).contiguous()
+        if v.dim() != 3 or v.shape[0] != B or v.shape[2] != 3:
+            raise ValueError("SilLossROI.set_occluder: (B,V,3) vertices for B = %d expected, got %s" % (B, tuple(v.shape)))
+        f32 = torch.as_tensor(faces).to(device=dev, dtype=torch.int32).reshape(-1, 3)
+        Fn, V = f32.shape[0], v.shape[1]
+        if not hasattr(self, "occ_depth"):
+            self.register_buffer("occ_depth", torch.empty(B, S, S, dtype=torch.float32, device=dev))
+            self.register_buffer("_occ_eye", torch.eye(3, device=dev).repeat(B, 1, 1), persistent=False)
+            self.register_buffer("_occ_zero", torch.zeros(B, 3, device=dev), persistent=False)
+            self.register_buffer("_occ_one", torch.ones(B, device=dev), persistent=False)
+        if getattr(self, "_occ_faces", None) is None or tuple(self._occ_faces.shape) != (B, Fn, 3):      # scratch, once per face count
+            self._occ_faces = torch.empty(B, Fn, 3, dtype=torch.int32, device=dev)
+            self._occ_tri = torch.empty(B, 2 * Fn, 3, 3, dtype=torch.float32, device=dev)
+            self._occ_fim = torch.empty(B, S, S, dtype=torch.int32, device=dev)
+            self._occ_alpha = torch.empty(B, S, S, dtype=torch.float32, device=dev)
+            self._occ_ws = torch.empty(max(_lib.lib.chore_silhouette_workspace_bytes(B, 2 * Fn), 1), dtype=torch.uint8, device=dev)
+        self._occ_faces.copy_(f32.unsqueeze(0).expand(B, -1, -1))
+        h = _lib.handle(dev.index or 0)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        bc = 1 if self.R.shape[0] == 1 else 0
+        _lib.check(_lib.lib.chore_sil_project_fwd(h, v.data_ptr(), self._occ_faces.data_ptr(), self._occ_eye.data_ptr(),
+                                                  self._occ_zero.data_ptr(), self._occ_one.data_ptr(), self.K.data_ptr(),
+                                                  self.R.data_ptr(), self.t.data_ptr(), bc, None, 1.0, 1e-9, B, V, Fn,
+                                                  self._occ_tri.data_ptr(), stream), h, "chore_sil_project_fwd")
+        _lib.check(_lib.lib.chore_silhouette_fwd(h, self._occ_tri.data_ptr(), B, 2 * Fn, S, NEAR, FAR, self._occ_fim.data_ptr(),
+                                                 self._occ_alpha.data_ptr(), self._occ_ws.data_ptr(), stream), h, "chore_silhouette_fwd")
+        _lib.check(_lib.lib.chore_sil_depth(h, self._occ_tri.data_ptr(), self._occ_fim.data_ptr(), B, 2 * Fn, S, FAR, 1,
+                                            self.occ_depth.data_ptr(), stream), h, "chore_sil_depth")
+        return self
+
+    def depth_loss(self, tri, face_index):
+        """PHOSA's ordinal depth term on the step's triangle list and winner map (render_parts / mask_loss(parts=True)) against
+        the occluder of set_occluder: {"depth": mean_b sum_pixels log1p(exp(min(violation, 2)))} over the pixels whose two depths
+        contradict the masks (person pixel: the object is in front of the body; object pixel: the body is in front of the
+        object), one launch pair each way (chore_ordinal_depth_fwd / _bwd).  Not a term of the reference's fit."""
+        if not hasattr(self, "occ_depth"):
+            raise RuntimeError("SilLossROI.depth_loss: call set_occluder first")
+        return {"depth": _OrdinalDepthFn.apply(tri, face_index, self.occ_depth, self.image_ref, self.keep_mask, DEPTH_CLAMP).mean()}
+
+    @torch.no_grad()
+    def depth_order_counts(self, R, obj_t, obj_s):
+        """(B,4) int32 of the pose: pixels in case A (person pixel, object in front), in case B (object pixel, body in front),
+        person pixels where both meshes project, object pixels where both do (chore_ordinal_depth_fwd's counts)"""
+        if not hasattr(self, "occ_depth"):
+            raise RuntimeError("SilLossROI.depth_order_counts: call set_occluder first")
+        _, tri, fim = self.render_parts(R, obj_t, obj_s)
+        return ordinal_depth_counts(tri, fim, self.occ_depth, self.image_ref, self.keep_mask)[2]
 
     def edge_loss(self, image):
         """PHOSA's edge term on the image mask_loss returns: {"edge": mean_b sum_pixels compute_edges(image) * edt_ref_edge},

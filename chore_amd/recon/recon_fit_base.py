@@ -363,8 +363,9 @@ class ReconFitterBase:
         smpl_files, obj_files = self.get_output_paths(image_paths, save_name, test_id)
         return all(os.path.isfile(sf) and os.path.isfile(of) for sf, of in zip(smpl_files, obj_files))
 
-    def save_outputs(self, smpl, obj_R, obj_t, traindata_paths, save_name, test_id, obj_s=None):
-        """fitted SMPL mesh + parameters and object mesh + parameters next to each other  [:258-275, opt_utils.py:73-101]"""
+    def save_outputs(self, smpl, obj_R, obj_t, traindata_paths, save_name, test_id, obj_s=None, images=None, crop_centers=None):
+        """fitted SMPL mesh + parameters and object mesh + parameters next to each other  [:258-275, opt_utils.py:73-101];
+        images (B,5,H,W) / crop_centers (B,2): the batch's, read by REPORT_DEPTH_ORDER only"""
         smpl_files, obj_files = self.get_output_paths(traindata_paths, save_name, test_id)
         smpl.forget()
         with torch.no_grad():
@@ -391,6 +392,17 @@ class ReconFitterBase:
                 frame = {k: None if v is None else {n: x[i] for n, x in v.items()} for k, v in rep.items()}
                 with open(sf.replace(".smpl.ply", ".penetration.json"), "w") as f:
                     json.dump(frame, f, indent=1)
+        if self.REPORT_DEPTH_ORDER:             # of the fitted body and pose against the batch's masks; draws no random numbers
+            if smpl.faces is None or images is None or crop_centers is None or obj_s is None:
+                raise RuntimeError("REPORT_DEPTH_ORDER needs the body model's faces, obj_s, and the batch's images and crop centres")
+            dev = self.device
+            images = torch.as_tensor(images).to(dev)
+            counts = self.depth_order_report(torch.as_tensor(verts, device=dev), smpl.faces, self.decopose_axis(obj_R, no_rand=True),
+                                             obj_t, obj_s, images[:, 3, :, :], images[:, 4, :, :],
+                                             torch.as_tensor(crop_centers).to(dev)).cpu().tolist()
+            for i, sf in enumerate(smpl_files):
+                with open(sf.replace(".smpl.ply", ".depth_order.json"), "w") as f:
+                    json.dump(self.depth_order_frame(counts[i]), f, indent=1)
         if self.REPORT_OCCLUSION:               # of the very meshes written above; draws no random numbers
             from .eval.occlusion import COUNT_KEYS, frame_report
             if smpl.faces is None:
@@ -449,6 +461,43 @@ class ReconFitterBase:
     # (PHOSA's sum(edges(rendered) * edt_ref_edge), which pulls the rendered outline onto the mask's), weighted by
     # get_loss_weights()["edge"].  False (the default): nothing is computed, no key appears, no fitted bit changes.
     SIL_EDGE_TERM = False
+
+    # True: optimize_smpl_object fills the silhouette term's occluder once per call (SilLossROI.set_occluder(body, faces): the
+    # body's depth image over the ROI cameras; the body does not move there and gets no gradient), and forward_step adds
+    # loss_dict["depth"] = SilLossROI.depth_loss -- PHOSA's ordinal depth term: where the person mask shows, the body is in
+    # front of the object; where the object mask shows, the object is -- in the 'sil' phase after "edge" (on the placement and
+    # rasterisation of the mask term) and in the 'joint' phase after "pen" (on its own), weighted by
+    # get_loss_weights()["depth"].  It needs SilLossROI's device path: a silhouette term without set_occluder, or
+    # CHORE_SIL_TORCH_PROJECT in the environment, is refused by optimize_smpl_object before any step.
+    # False (the default): nothing is computed, no key appears, no fitted bit changes.
+    ORDINAL_DEPTH_TERM = False
+
+    # True: save_outputs (given the batch's images and crop centres) also writes k{test_id}.depth_order.json next to the PLY
+    # files: per frame the four pixel counts of the fitted meshes (depth_order_report) and the two violated fractions.  The fit
+    # itself never reads it: no fitted bit changes.
+    REPORT_DEPTH_ORDER = False
+
+    def depth_order_report(self, smpl_verts, smpl_faces, obj_R, obj_t, obj_s, person_masks, obj_masks, crop_centers):
+        """body vertices (B,V,3) and faces, the object pose (obj_R: rotation matrices), the (B,H,W) network-input masks and
+        (B,2) crop centres -> (B,4) int32 device tensor: pixels of the silhouette term's grid in case A (a person pixel where the
+        object is in front of the body), in case B (an object pixel where the body is in front), person pixels where both meshes
+        project, object pixels where both do (chore_ordinal_depth_fwd's counts).  No gradient."""
+        from .obj_pose_roi import SilLossROI
+        if self.scan is None:
+            raise RuntimeError("depth_order_report needs the object template mesh (scan_verts / scan_faces)")
+        with torch.no_grad():
+            sil = SilLossROI.from_masks(person_masks, obj_masks, self.scan, crop_centers, rend_size=self.SIL_REND_SIZE,
+                                        device=self.device, crop_size=self.camera.crop_size)
+            sil.set_occluder(smpl_verts.detach(), smpl_faces)
+            return sil.depth_order_counts(obj_R.detach().float(), obj_t.detach().float(), obj_s.detach().float().reshape(-1))
+
+    @staticmethod
+    def depth_order_frame(counts4):
+        """one frame's counts -> the report's dict; a fraction is None where its denominator is 0"""
+        a, b, pb, ob = (int(x) for x in counts4)
+        return {"person_pixels_object_in_front": a, "object_pixels_body_in_front": b, "person_pixels_both": pb,
+                "object_pixels_both": ob, "person_violated_fraction": a / pb if pb else None,
+                "object_violated_fraction": b / ob if ob else None}
 
     def _template_closed(self):
         """is the template a closed mesh (is_closed)?  Checked on the host once per template -- before any step is recorded"""

@@ -208,7 +208,10 @@ class ReconFitterBehave(ReconFitterBase):
              "pen": 30.0 ** 2,
              # "edge" (SIL_EDGE_TERM, not in the reference): the coefficient this table gives "mask", the other term that is a
              # sum over the pixels of the rendering.  Not tuned.
-             "edge": 0.003 ** 2}
+             "edge": 0.003 ** 2,
+             # "depth" (ORDINAL_DEPTH_TERM, not in the reference): likewise a sum over pixels, likewise the coefficient of "mask".
+             # Not tuned, no fit quality claimed.
+             "depth": 0.003 ** 2}
         return {k: (lambda cst, it, c=c: c * cst / (1 + it)) for k, c in w.items()}
 
     # ---- the whole chain ------------------------------------------------------------------------------
@@ -250,7 +253,11 @@ class ReconFitterBehave(ReconFitterBase):
         def finish(i, data, fitted):
             smpl, obj_R, obj_t, obj_s = fitted
             if save and self.outpath is not None:
-                self.save_outputs(smpl, obj_R, obj_t, data["path"], args.save_name, args.test_kid, obj_s)
+                if self.REPORT_DEPTH_ORDER:        # the report reads the batch's masks
+                    self.save_outputs(smpl, obj_R, obj_t, data["path"], args.save_name, args.test_kid, obj_s,
+                                      images=data.get("images"), crop_centers=data.get("crop_center"))
+                else:
+                    self.save_outputs(smpl, obj_R, obj_t, data["path"], args.save_name, args.test_kid, obj_s)
             results.append(dict(index=i, pose=smpl.pose.detach(), betas=smpl.betas.detach(), trans=smpl.trans.detach(),
                                 obj_R=self.decopose_axis(obj_R, no_rand=True).detach(), obj_t=obj_t.detach(),
                                 obj_s=obj_s.detach()))
@@ -731,12 +738,18 @@ class ReconFitterBehave(ReconFitterBase):
         R = self.project_so3(rot_noisy) if rot_noisy is not None else self.decopose_axis(obj_R, noise=noise)
         if phase == "sil":      # none of its terms reads the field (the reference queries the object points all the same, :171)
             sil = data_dict["silhouette"]
-            obj_losses, image = sil.mask_loss(R, obj_t, obj_s) if hasattr(sil, "mask_loss") else sil(R, obj_t, obj_s)[:2]
+            depth_on = self.ORDINAL_DEPTH_TERM and hasattr(sil, "occ_depth")      # (optimize_smpl_object filled it, or refused)
+            if depth_on:                   # opt-in: the mask term also hands out its triangle list and winner map
+                obj_losses, image, tri, fim = sil.mask_loss(R, obj_t, obj_s, parts=True)
+            else:
+                obj_losses, image = sil.mask_loss(R, obj_t, obj_s) if hasattr(sil, "mask_loss") else sil(R, obj_t, obj_s)[:2]
             loss_dict["mask"] = obj_losses["mask"]
             loss_dict["scale"] = torch.mean((obj_s - self.obj_scale) ** 2)
             loss_dict["trans"] = torch.mean((obj_t - data_dict["trans_init"]) ** 2)
             if self.SIL_EDGE_TERM:         # opt-in: PHOSA's edge term on the image the mask term rendered
                 loss_dict["edge"] = sil.edge_loss(image)["edge"]
+            if depth_on:                   # opt-in: PHOSA's ordinal depth term on the same placement and rasterisation
+                loss_dict["depth"] = sil.depth_loss(tri, fim)["depth"]
             return loss_dict
         object = self.transform_obj_verts(data_dict["objects"], R, obj_t, obj_s)
         model.query(object, **data_dict["query_dict"])
@@ -769,6 +782,11 @@ class ReconFitterBehave(ReconFitterBase):
                 loss_dict["collide"] = self.compute_collision_loss(smpl_verts, smpl.faces, R, obj_t, obj_s)
                 if self.PENETRATION_TERM:      # opt-in: the exact depth the penetration report prints, as a term
                     loss_dict["pen"] = self.compute_penetration_loss(smpl_verts, smpl.faces, R, obj_t, obj_s)
+            sil = data_dict.get("silhouette")
+            if self.ORDINAL_DEPTH_TERM and sil is not None and hasattr(sil, "occ_depth"):
+                # opt-in: the ordinal depth term on a placement and rasterisation of its own (this phase has no mask term)
+                _, tri, fim = sil.render_parts(R, obj_t, obj_s)
+                loss_dict["depth"] = sil.depth_loss(tri, fim)["depth"]
         return loss_dict
 
     def optimize_smpl_object(self, model, data_dict, obj_iter=20, joint_iter=10, steps_per_iter=10, sil_iter=50,
@@ -819,7 +837,7 @@ class ReconFitterBehave(ReconFitterBase):
             slot = self._slot("object", tuple(obj_R.shape), tuple(data_dict["objects"].shape), tuple(body.shape), str(obj_R.device),
                               self._maps_key(model), obj_iter, joint_iter, steps_per_iter, sil_iter, max_iter, sil_key,
                               bool(self.PENETRATION_TERM),     # kept graphs of one setting are not replayed under the other
-                              bool(self.SIL_DEVICE_SETUP), bool(self.SIL_EDGE_TERM))
+                              bool(self.SIL_DEVICE_SETUP), bool(self.SIL_EDGE_TERM), bool(self.ORDINAL_DEPTH_TERM))
         if sil_masks is not None:
             if slot is None or "silhouette" not in slot.objects:
                 sil = SilLossROI.from_masks(sil_masks[0], sil_masks[1], self.scan, sil_masks[2], rend_size=self.SIL_REND_SIZE,
@@ -827,7 +845,22 @@ class ReconFitterBehave(ReconFitterBase):
             else:                             # the kept term, refreshed in place: the recorded steps read its buffers
                 sil = slot.objects["silhouette"].set_masks(*sil_masks)
             data_dict["silhouette"] = sil
+
+        def occlude(term):
+            # ORDINAL_DEPTH_TERM: the body's depth image over the term's ROI cameras, once per call and outside the recorded steps
+            # (the body does not move in this function); a kept term has its buffer refreshed in place
+            if self.ORDINAL_DEPTH_TERM and term is not None:
+                # one clear error up front instead of a silent fall-back: the term needs SilLossROI's device path
+                if not hasattr(term, "set_occluder"):
+                    raise RuntimeError("ORDINAL_DEPTH_TERM needs a silhouette term with set_occluder / depth_loss (SilLossROI), got %s"
+                                       % type(term).__name__)
+                if os.environ.get("CHORE_SIL_TORCH_PROJECT"):
+                    raise RuntimeError("ORDINAL_DEPTH_TERM shares the placement kernel's triangle list: unset CHORE_SIL_TORCH_PROJECT")
+                if split.faces is None:
+                    raise RuntimeError("ORDINAL_DEPTH_TERM needs the body model's faces")
+                term.set_occluder(body, split.faces)
         if slot is None:
+            occlude(sil)
             self._optimize_object(model, split, data_dict, None, obj_R, obj_t, obj_s, obj_iter, joint_iter, steps_per_iter,
                                   sil_iter, max_iter)
         else:
@@ -842,6 +875,7 @@ class ReconFitterBehave(ReconFitterBase):
                 kept = slot.obj("silhouette", lambda: sil)
                 if kept is not sil:
                     kept.load_from(sil)
+                occlude(kept)
                 dd["silhouette"] = kept
             pR, pt, ps = slot.bind("obj_R", obj_R, leaf=True), slot.bind("obj_t", obj_t, leaf=True), slot.bind("obj_s", obj_s, leaf=True)
             for p_ in (pR, pt, ps):

@@ -34,4 +34,6 @@ class ReconFitterCoco(ReconFitterBehave):
             w["pen"] = 30.0 ** 2        # in recon_fit_behave.py (that of a mean of distances in metres there), not tuned
         if self.SIL_EDGE_TERM:          # likewise not in the reference: the coefficient this table gives "mask", the other term
             w["edge"] = 0.3 ** 2        # that is a sum over the pixels of the rendering, not tuned
+        if self.ORDINAL_DEPTH_TERM:     # likewise: a sum over pixels, the coefficient of "mask", not tuned
+            w["depth"] = 0.3 ** 2
         return {k: (lambda cst, it, c=c: c * cst / (1 + it)) for k, c in w.items()}

@@ -359,6 +359,44 @@ int chore_sil_edge_bwd(chore_handle* h, const float* weight, const int* argmax, 
                        float* g_image, chore_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * PHOSA's ordinal depth term for the object fit: the masks say who is in front  (not in the reference's fit; PHOSA's
+ * losses.py compute_ordinal_depth_loss is the model).  On the S x S grid of the silhouette term, per frame:
+ *   d_o(p)  depth of the object face that wins pixel p: the face chore_silhouette_fwd writes for the step's triangle list
+ *           `tri` (B,F,3,3), and zp of the depth rule of chore_render_fwd (clamped, renormalised barycentric weights from the
+ *           pixel-space inverse, 1 / sum w_k / z_k) -- the value chore_render_fwd writes at ssaa 1, bit for bit;
+ *   d_h(p)  occluder_depth (B,S,S): the same quantity of the body, far_z where there is no body; a constant, no gradient;
+ *   both    an object face won (face_index in [0, F)) and d_h < far_z;
+ *   O = image_ref > 0.5 (the object), P = not O and keep_mask < 0.5 (the person without the object: a pixel the crops label
+ *           both ways counts as object, as for the mask term -- the one difference from PHOSA's mask_i & ~mask_j);
+ *   case A  P and both and d_o < d_h: x = min(d_h - d_o, c), term log1p(exp(x)), d term / d d_o = -sigmoid(x) if d_h - d_o <= c, else 0;
+ *   case B  O and both and d_h < d_o: x = min(d_o - d_h, c), the same with the sign +.   Equal depths contribute nothing.
+ * Orientation: face_index is chore_silhouette_fwd's (rows NOT flipped); occluder_depth, image_ref, keep_mask and coef are in
+ * the orientation of SilLossROI.image_ref, i.e. their row r is row S - 1 - r of face_index.  S <= 4096, B <= 65535.
+ * Every call runs on `stream`, allocates nothing, reads no device value on the host (it can be captured into a graph), uses
+ * no float atomics and returns CHORE_EINVAL before any launch for NULL pointers and shapes it does not take.
+ *
+ * chore_sil_depth: depth[b, r, x] = d of the winner face_index[b, y, x], far_z where it is -1; r = S - 1 - y if flip_rows,
+ *   else y.  With flip_rows it equals the depth image of chore_render_fwd at ssaa 1 bit for bit.  Fills occluder_depth.
+ * chore_ordinal_depth_fwd: per_frame_sum (B) = the sum of the terms over the frame's pixels; coef (B,S,S) = d term / d d_o, 0
+ *   wherever neither case holds; counts (B,4) int32 = pixels in case A, in case B, in P and both, in O and both.  The sum is a
+ *   tree over blocks of 256 pixels (8 additions deep), then per frame thread t adds block sums t, t + 256, ... and the same
+ *   tree follows: the longest chain is 16 + ceil(ceil(S^2 / 256) / 256) additions.  expf / log1pf are the device library's.
+ *   0 < c <= 80.  workspace: chore_ordinal_depth_workspace_bytes(B, S) (0 = unsupported shape).
+ * chore_ordinal_depth_bwd: grad_tri (B,F,3,3), overwritten = the depth rule of chore_render_bwd, all three components, applied
+ *   to the per-pixel depth gradient coef[b, r, x] * g_per_frame[b] (one float product): bit for bit what chore_render_bwd gives
+ *   for that product as grad_depth alone.  Gathered per face: a workgroup walks the face's box, every thread adds the pixels
+ *   the face won in tile order, then a fixed butterfly per wave and the four waves in order.  Faces that won nothing get zeros.
+ * ------------------------------------------------------------------------------------------- */
+int chore_sil_depth(chore_handle* h, const float* tri, const int* face_index, int B, int F, int S, float far_z, int flip_rows,
+                    float* depth, chore_stream_t stream);
+size_t chore_ordinal_depth_workspace_bytes(int B, int S);
+int chore_ordinal_depth_fwd(chore_handle* h, const float* tri, const int* face_index, const float* occluder_depth,
+                            const float* image_ref, const float* keep_mask, int B, int F, int S, float far_z, float c,
+                            float* per_frame_sum, float* coef, int* counts, void* workspace, chore_stream_t stream);
+int chore_ordinal_depth_bwd(chore_handle* h, const float* tri, const int* face_index, const float* coef, const float* g_per_frame,
+                            int B, int F, int S, float* grad_tri, chore_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Colour / depth / coverage rendering of meshes  (replaces what Renderer.render gets from neural_renderer's
  * rasterize_rgbad, external/neural_renderer/neural_renderer/rasterize.py:267-348: forward_face_index_map,
  * forward_texture_sampling, forward_background and forward_alpha_map of cuda/rasterize_cuda_kernel.cu:24-288 at image
