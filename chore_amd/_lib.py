@@ -229,6 +229,8 @@ SIGNATURES = {
                                [c_float] * 4 + [c_void_p] * 2 + [c_int] + [c_void_p] * 6),
     "chore_instances_workspace_bytes": (c_size_t, [c_int] * 5),
     "chore_instances_fwd": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_float] * 2 + [c_void_p] * 7),
+    "chore_photo_textures_fwd": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_float] * 3 + [c_int] + [c_void_p] * 3),
+    "chore_point_visibility": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_float] * 3 + [c_void_p] * 2),
     "chore_mesh_dist_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "chore_mesh_dist_fwd": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 6),
     "chore_mesh_sdf_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),

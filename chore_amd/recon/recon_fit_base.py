@@ -721,6 +721,8 @@ class ReconFitterBase:
     # visualize_fit_scene: how many meshes a sample shows through each other (Renderer.render_scene's face_layers, one layer per
     # mesh).  1 = a translucent mesh hides every mesh behind it; set it to 4, say, to see the object through the body
     VIEW_FACE_LAYERS = 1
+    # with -d, also write k{tid}.debug_photo.png per frame (visualize_photo_fit): the fitted meshes wearing the input photo
+    VIEW_PHOTO_TEXTURES = False
     _view_index = 0
     debug_dest = None                             # (save_name, test_id) of the debug files; fit_recon sets it from its args
 
@@ -849,6 +851,26 @@ class ReconFitterBase:
                                   markers, point_depth_bias=self.VIEW_POINT_BIAS, camera=self.camera,
                                   face_layers=self.VIEW_FACE_LAYERS)
 
+    def visualize_photo_fit(self, data_dict, object_verts, smpl_verts, smpl_faces=None):
+        """the fitted SMPL mesh (`smpl_verts` (B,V,3) with `smpl_faces` (F,3); left out without faces) and the object template under
+        the fitted pose (`object_verts` (B,V,3) with self.scan_faces, or None) coloured from the input photo wherever the
+        network's camera sees them, next to that photo
+        (utils/render_utils.render_photo_views): a body slid along the viewing ray or a misplaced object wears the wrong patch of
+        image.  Hidden texels keep SMPL_OBJ_COLOR_LIST's colours; VIEW_POINT_BIAS (metres, not tuned) is how far behind the
+        nearest surface a texel may lie and still count as seen.  -> (512, 1152, 3) uint8"""
+        from ..utils.render_utils import SMPL_OBJ_COLOR_LIST, Mesh, render_photo_views
+        idx = self._view_index
+        host = lambda x: np.asarray(x.detach().cpu()) if torch.is_tensor(x) else np.asarray(x)     # noqa: E731
+        meshes, mesh_colors = [], []
+        if smpl_faces is not None:
+            meshes.append(Mesh(v=host(smpl_verts[idx]), f=host(smpl_faces)))
+            mesh_colors.append(SMPL_OBJ_COLOR_LIST[0])
+        if object_verts is not None and self.scan_faces is not None:
+            meshes.append(Mesh(v=host(object_verts[idx]), f=host(self.scan_faces)))
+            mesh_colors.append(SMPL_OBJ_COLOR_LIST[1])
+        return render_photo_views(data_dict["images"][idx], data_dict["query_dict"]["crop_center"][idx], meshes, mesh_colors,
+                                  depth_bias=self.VIEW_POINT_BIAS, camera=self.camera)
+
     def _contact_view_data(self, data_dict, model, obj_center_pred, object, smpl, smpl_verts):
         """what visualize_contact_fitting adds to data_dict for the whole batch: the contact masks (two field queries) and the
         three centres; the network's query state is restored"""
@@ -934,7 +956,8 @@ class ReconFitterBase:
             smpl.forget()
 
     def debug_after_object(self, prep, data_dict, smpl, obj_R, obj_t, obj_s):
-        """after optimize_smpl_object: k{tid}.debug_object.png and k{tid}.debug_fit.png (visualize_fit_scene) per frame"""
+        """after optimize_smpl_object: k{tid}.debug_object.png and k{tid}.debug_fit.png (visualize_fit_scene) per frame, and with
+        VIEW_PHOTO_TEXTURES k{tid}.debug_photo.png (visualize_photo_fit)"""
         if not self._debug_on():
             return
         from ..utils.render_utils import write_png
@@ -963,6 +986,10 @@ class ReconFitterBase:
                 for i, f in enumerate(self._debug_files(paths, "fit")):
                     self._view_index = i
                     write_png(f, self.visualize_fit_scene(dd, scan, smpl, verts))
+                if self.VIEW_PHOTO_TEXTURES:
+                    for i, f in enumerate(self._debug_files(paths, "photo")):
+                        self._view_index = i
+                        write_png(f, self.visualize_photo_fit(dd, scan, verts, smpl.faces))
         finally:
             self._view_index = 0
             model.preds, model.points, model.intermediate_preds_list = kept

@@ -1,5 +1,5 @@
 """the names `import neural_renderer as nr` gives the reference's visualisation code (utils/render_utils.py)"""
 from ..recon.obj_pose_roi import projection, vertices_to_faces  # noqa: F401
 from .renderer import (Renderer, face_light, face_visibility, get_points_from_angles, lighting, look, look_at,  # noqa: F401
-                       perspective, rasterize_instances, rasterize_rgbad, rasterize_scene, splat_points,
-                       world_radius_to_pixels)
+                       perspective, photo_textures, point_visibility, rasterize_instances, rasterize_rgbad, rasterize_scene,
+                       sample_depth, splat_points, world_radius_to_pixels)

@@ -11,7 +11,9 @@ rasterisation goes through `_RasterizeRGBAD` (chore_render_fwd + chore_render_bw
 `render_silhouettes` and `rasterize_rgbad` carry gradients; otherwise the call is the plain forward.  The point and scene
 renderers (`splat_points`, `rasterize_scene`, `render_points`, `render_scene`) are forward only and detach their inputs, and so
 are visibility and instance masks (`face_visibility`, `rasterize_instances`, `Renderer.visibility`, `Renderer.render_instances`:
-chore_instances_fwd; the reference's visibility.py:12-34 and renderer.py:79-117).
+chore_instances_fwd; the reference's visibility.py:12-34 and renderer.py:79-117), and textures taken from a photo with the
+per-texel and per-point visibility under them (`sample_depth`, `photo_textures`, `point_visibility`, `Renderer.photo_textures`,
+`Renderer.vertex_visibility`: chore_photo_textures_fwd / chore_point_visibility, this package's own).
 
 Kept quirks of the reference: `light_direction` is used un-normalised; face normals are
 normalize(cross(v0 - v1, v2 - v1), eps=1e-5), dividing by max(norm, eps); lighting sees the world vertices, before the camera.
@@ -405,6 +407,101 @@ def face_visibility(faces, image_size, near=DEFAULT_NEAR, far=DEFAULT_FAR, eps=1
     return (out["face_samples"] > 0).to(torch.int32)
 
 
+VISIBILITY_DEPTH_BIAS = 0.02      # depth units of the triangles (metres in camera views): the fitter's VIEW_POINT_BIAS, not tuned
+
+
+def _projected_faces(faces):
+    if not faces.is_cuda:
+        raise RuntimeError("chore_amd needs device tensors (no CPU path)")
+    tri = faces.detach().float().contiguous()
+    if tri.dim() != 4 or tuple(tri.shape[2:]) != (3, 3) or tri.shape[0] < 1 or tri.shape[1] < 1:
+        raise ValueError("faces (B,F,3,3) expected, got %s" % (tuple(tri.shape),))
+    return tri
+
+
+def _depth_image(depth, dev, B):
+    d = depth.detach().to(dev).float().contiguous()
+    if d.dim() != 3 or d.shape[0] != B or d.shape[1] != d.shape[2]:
+        raise ValueError("depth (B,S,S) with B = %d expected, got %s" % (B, tuple(d.shape)))
+    if not 1 <= d.shape[1] <= 4096:
+        raise ValueError("depth: S must lie in 1..4096, got %d" % d.shape[1])
+    return d
+
+
+def sample_depth(faces, image_size, near=DEFAULT_NEAR, far=DEFAULT_FAR):
+    """faces (B,F,3,3) projected triangles -> (B,S,S) depth of the nearest face per sample of the image_size grid without
+    anti-aliasing, rows NOT flipped, `far` where there is none: the depth image `photo_textures` and `point_visibility` test
+    against (chore_silhouette_fwd + chore_sil_depth; `rasterize_rgbad`'s depth at anti_aliasing=False with the rows reversed).
+    Forward only: the input is detached."""
+    tri = _projected_faces(faces)
+    dev, S = tri.device, int(image_size)
+    if not 1 <= S <= 4096:
+        raise ValueError("image_size must lie in 1..4096, got %r" % (image_size,))
+    B, Fn = tri.shape[:2]
+    h = _lib.handle(dev.index or 0)
+    fim = torch.empty(B, S, S, dtype=torch.int32, device=dev)
+    alpha = torch.empty(B, S, S, dtype=torch.float32, device=dev)
+    depth = torch.empty(B, S, S, dtype=torch.float32, device=dev)
+    ws = torch.empty(max(_lib.lib.chore_silhouette_workspace_bytes(B, Fn), 1), dtype=torch.uint8, device=dev)
+    _lib.check(_lib.lib.chore_silhouette_fwd(h, tri.data_ptr(), B, Fn, S, float(near), float(far), fim.data_ptr(), alpha.data_ptr(),
+                                             ws.data_ptr(), _stream(dev)), h, "chore_silhouette_fwd")
+    _lib.check(_lib.lib.chore_sil_depth(h, tri.data_ptr(), fim.data_ptr(), B, Fn, S, float(far), 0, depth.data_ptr(), _stream(dev)),
+               h, "chore_sil_depth")
+    return depth
+
+
+def photo_textures(faces, depth, photo, fallback, texture_size=4, depth_bias=VISIBILITY_DEPTH_BIAS, near=DEFAULT_NEAR,
+                   far=DEFAULT_FAR, align_corners=False, return_visible=False):
+    """the texture cube of every face filled from a photo at the texels the camera sees (chore_photo_textures_fwd; the rule is
+    written down in include/chore_hip.h).  faces (B,F,3,3) projected triangles as `rasterize_rgbad` takes them; depth (B,S,S)
+    from `sample_depth` (of these faces or of a larger scene that hides them); photo (B,3,Hp,Wp) in the orientation of an
+    image (row 0 on top): Wp is the side of the square [-1,1]^2 maps to, of which the upper Hp <= Wp rows exist; fallback
+    (B,F,3): the colour of a texel that is hidden, out of view or outside the photo.  depth_bias is in the depth units of the
+    triangles (metres in camera views); 0.02 is the fitter's VIEW_POINT_BIAS, not tuned.  align_corners=True reads the photo
+    under grid_sample's align_corners=True convention, which KinectColorCamera.project_points produces.
+    -> textures (B,F,ts,ts,ts,3) [, visible (B,F,ts,ts,ts) bool].  Forward only: the inputs are detached."""
+    tri = _projected_faces(faces)
+    dev = tri.device
+    B, Fn = tri.shape[:2]
+    ts = int(texture_size)
+    if not 2 <= ts <= 16:
+        raise ValueError("texture_size must lie in 2..16, got %r" % (texture_size,))
+    d = _depth_image(depth, dev, B)
+    ph = photo.detach().to(dev).float().contiguous()
+    if ph.dim() != 4 or ph.shape[0] != B or ph.shape[1] != 3 or ph.shape[2] < 1 or ph.shape[2] > ph.shape[3]:
+        raise ValueError("photo (B,3,Hp,Wp) with B = %d and 1 <= Hp <= Wp expected, got %s" % (B, tuple(ph.shape)))
+    fb = _opt(fallback, dev, (B, Fn, 3), "fallback")
+    if fb is None:
+        raise ValueError("fallback (B,F,3) expected")
+    tex = torch.empty(B, Fn, ts, ts, ts, 3, dtype=torch.float32, device=dev)
+    vis = torch.empty(B, Fn, ts, ts, ts, dtype=torch.uint8, device=dev) if return_visible else None
+    h = _lib.handle(dev.index or 0)
+    _lib.check(_lib.lib.chore_photo_textures_fwd(h, tri.data_ptr(), d.data_ptr(), ph.data_ptr(), fb.data_ptr(), B, Fn, ts,
+                                                 d.shape[1], ph.shape[2], ph.shape[3], float(near), float(far), float(depth_bias),
+                                                 1 if align_corners else 0, tex.data_ptr(), _ptr(vis), _stream(dev)),
+               h, "chore_photo_textures_fwd")
+    return (tex, vis.bool()) if return_visible else tex
+
+
+def point_visibility(points, depth, depth_bias=VISIBILITY_DEPTH_BIAS, near=DEFAULT_NEAR, far=DEFAULT_FAR):
+    """projected points (B,N,3) [u, v in [-1,1], depth] against a depth image (B,S,S) from `sample_depth` -> (B,N) int32, 1 where
+    the point is in view, between near and far, and not more than depth_bias behind the nearest face of its sample
+    (chore_point_visibility: the rule `photo_textures` applies to a texel).  depth_bias as in `photo_textures`.  Forward only."""
+    if not points.is_cuda:
+        raise RuntimeError("chore_amd needs device tensors (no CPU path)")
+    pts = points.detach().float().contiguous()
+    if pts.dim() != 3 or pts.shape[2] != 3 or pts.shape[0] < 1 or pts.shape[1] < 1:
+        raise ValueError("points (B,N,3) expected, got %s" % (tuple(pts.shape),))
+    dev = pts.device
+    B, N = pts.shape[:2]
+    d = _depth_image(depth, dev, B)
+    out = torch.empty(B, N, dtype=torch.int32, device=dev)
+    h = _lib.handle(dev.index or 0)
+    _lib.check(_lib.lib.chore_point_visibility(h, pts.data_ptr(), d.data_ptr(), B, N, d.shape[1], float(near), float(far),
+                                               float(depth_bias), out.data_ptr(), _stream(dev)), h, "chore_point_visibility")
+    return out
+
+
 def world_radius_to_pixels(world_radius, z, focal_px):
     """pixel radius of a sphere of `world_radius` metres at depth z under a focal length of `focal_px` OUTPUT pixels:
     focal_px * world_radius / z, so points shrink with distance"""
@@ -544,6 +641,38 @@ class Renderer(nn.Module):
             face_group = torch.as_tensor(face_group).to(vertices.device)
         tri, face_group = self._project_faces(vertices, faces, (K, R, t, dist_coeffs, orig_size), face_group)
         return rasterize_instances(tri, face_group, num_groups, self.image_size, self.anti_aliasing, self.near, self.far)
+
+    def _visibility_depth(self, vertices, faces, visibility_size, cam):
+        """projected vertices (B,V,3), detached, and the depth image of the mesh (both windings under fill_back) at
+        visibility_size (None: image_size), without anti-aliasing"""
+        ndc = self.transform(vertices.detach().float(), *cam)
+        faces = faces.detach()
+        both = torch.cat((faces, faces.flip(-1)), dim=1) if self.fill_back else faces
+        S = self.image_size if visibility_size is None else visibility_size
+        return ndc, sample_depth(vertices_to_faces(ndc, both), S, self.near, self.far)
+
+    def photo_textures(self, vertices, faces, photo, fallback=None, texture_size=4, depth_bias=VISIBILITY_DEPTH_BIAS,
+                       visibility_size=None, K=None, R=None, t=None, dist_coeffs=None, orig_size=None, align_corners=False,
+                       return_visible=False):
+        """the camera path of `render`, then `photo_textures`: textures (B,F,ts,ts,ts,3) for the F faces given, coloured from
+        `photo` (B,3,Hp,Wp) where this camera sees them, so `render(vertices, faces, textures)` doubles them under fill_back as
+        it does any textures.  The depth image is taken over both windings under fill_back, at visibility_size (None:
+        image_size) without anti-aliasing.  fallback: one colour (3,), (B,F,3), or None = mid grey.  depth_bias: depth units of
+        the camera (metres in camera views); 0.02 is the fitter's VIEW_POINT_BIAS, not tuned.  Forward only."""
+        ndc, depth = self._visibility_depth(vertices, faces, visibility_size, (K, R, t, dist_coeffs, orig_size))
+        B, Fn = faces.shape[:2]
+        fb = torch.as_tensor((0.5, 0.5, 0.5) if fallback is None else fallback, dtype=torch.float32).to(ndc.device)
+        if fb.dim() == 1:
+            fb = fb.view(1, 1, 3).expand(B, Fn, 3)
+        return photo_textures(vertices_to_faces(ndc, faces.detach()), depth, photo, fb, texture_size, depth_bias, self.near,
+                              self.far, align_corners, return_visible)
+
+    def vertex_visibility(self, vertices, faces, depth_bias=VISIBILITY_DEPTH_BIAS, visibility_size=None, K=None, R=None, t=None,
+                          dist_coeffs=None, orig_size=None):
+        """-> (B,V) int32: 1 where the vertex is in view and not more than depth_bias behind the nearest face of its sample
+        (`point_visibility` against the mesh's own depth image, both windings under fill_back).  Forward only."""
+        ndc, depth = self._visibility_depth(vertices, faces, visibility_size, (K, R, t, dist_coeffs, orig_size))
+        return point_visibility(ndc, depth, depth_bias, self.near, self.far)
 
     def focal_pixels(self, K=None, orig_size=None):
         """focal length in pixels of THIS renderer's output: K[0,0] scaled from `orig_size` to image_size in projection

@@ -432,6 +432,44 @@ def render_scene_views(images_b, crop_center_b, meshes, mesh_colors, mesh_opacit
     return np.concatenate([front, _side_crop(rgb, S)], axis=1)
 
 
+def render_photo_views(images_b, crop_center_b, meshes, mesh_colors, texture_size=TEXTURE_SIZE, depth_bias=0.02, side_renderer=None,
+                       camera=None, maxd=1.5):
+    """the fitted meshes of ONE frame wearing the photo they were fitted to -> (512, 512 + 640, 3) uint8: the input photo on the
+    left, the side view of `render_scene_views` (same y-flip, scale and centring) on the right, where a misfit shows as the wrong
+    patch of image on the wrong part of a mesh.
+
+    images_b (C,H,W) network input of the frame (channels 0..2 RGB in [0,1]), crop_center_b (2,), meshes with .v (camera space)
+    / .f, mesh_colors one colour each.  Every texel the network's camera sees takes the photo's colour there
+    (`nr.photo_textures` on the `_input_view_ndc` triangles, align_corners=True like the network's own
+    grid_sample, visibility on the CLOUD_VIEW_SIZE grid over both windings); every other texel -- hidden, out of the crop -- takes
+    the mesh colour times the side renderer's face light.  The side view is then rasterised WITHOUT light, so the photo is not
+    lit a second time.  depth_bias: metres; 0.02 is the fitter's VIEW_POINT_BIAS, not tuned."""
+    if not meshes:
+        raise ValueError("render_photo_views needs at least one mesh")
+    dev = images_b.device
+    camera = KinectColorCamera() if camera is None else camera
+    verts, faces, textures = mesh_tensors(meshes, mesh_colors, dev)
+    S, near, far = CLOUD_VIEW_SIZE, nr.renderer.DEFAULT_NEAR, nr.renderer.DEFAULT_FAR
+    blank = {"rgb": torch.zeros(1, 3, S, S, device=dev), "alpha": torch.zeros(1, S, S, device=dev)}
+    front = _over_photo(blank, images_b, S)
+
+    side_renderer = setup_side_renderer(2.0, 0., 90.) if side_renderer is None else side_renderer
+    _, place = _side_normalisation(verts[0], maxd)
+    side_verts = place(verts[0])[None]
+    light = nr.face_light(nr.vertices_to_faces(side_verts, faces), side_renderer.light_intensity_ambient,
+                          side_renderer.light_intensity_directional, side_renderer.light_color_ambient,
+                          side_renderer.light_color_directional, side_renderer.light_direction)
+    ndc = _input_view_ndc(camera, verts[0], crop_center_b)
+    depth = nr.sample_depth(nr.vertices_to_faces(ndc, torch.cat((faces, faces.flip(-1)), dim=1)), S, near, far)
+    photo = images_b[:3].detach().float().clamp(0, 1)[None]
+    textures = nr.photo_textures(nr.vertices_to_faces(ndc, faces), depth, photo, textures[:, :, 0, 0, 0, :] * light, texture_size,
+                                 depth_bias, near, far, align_corners=True)
+    tri, tex, _, _ = side_renderer._prepare_faces(side_verts, faces, textures, (None,) * 5)
+    rgb = nr.rasterize_rgbad(tri, tex, None, side_renderer.image_size, side_renderer.anti_aliasing, side_renderer.near,
+                             side_renderer.far, side_renderer.rasterizer_eps, side_renderer.background_color)["rgb"]
+    return np.concatenate([front, _side_crop(rgb, S)], axis=1)
+
+
 def _resize_u8(img, dsize, device):
     """cv2.resize(img, dsize) for uint8 images; equal sizes are a copy (as in cv2)"""
     if (img.shape[1], img.shape[0]) == (int(dsize[0]), int(dsize[1])):

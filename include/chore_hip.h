@@ -591,6 +591,42 @@ int chore_instances_fwd(chore_handle* h, const float* tri, const int* face_group
                         int* sample_face_index, void* workspace, chore_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Photo textures and point visibility, forward only: the texture cube of every face filled from a photo at the texels the
+ * camera sees, and whether a projected point is seen.  (The rule is this library's own; neural_renderer has no counterpart.)
+ * tri (B,F,3,3) projected triangles [u, v in [-1,1], depth], chore_render_fwd's; depth (B,S,S) depth of the nearest face per
+ * sample of the ssaa-1 grid, rows NOT flipped, far_z where there is none: what chore_silhouette_fwd + chore_sil_depth(...,
+ * flip_rows = 0) give, and chore_render_fwd at ssaa 1 with the rows reversed; photo (B,3,Hp,Wp) fp32 planar, Wp the side of the
+ * square [-1,1]^2 maps to, of which the upper Hp <= Wp rows exist; fallback (B,F,3): the colour of a texel that gets none from the
+ * photo; depth_bias in the depth units of the triangles; textures (B,F,ts,ts,ts,3): chore_render_fwd's layout; texel_visible
+ * (B,F,ts,ts,ts) bytes 0 / 1, or NULL.  pts (B,N,3) projected points; visible (B,N) int32 0 / 1.
+ * Texel (i,j,k) of face f of image b, vertices (u_k, v_k, z_k); all arithmetic fp32, each operation rounded once (no
+ * contraction), sums of three from the left:
+ *   1. weights: w = (i,j,k) / (i+j+k); the texel (0,0,0) takes (1/3,1/3,1/3).  The renderer samples the cube at
+ *      w_k (ts-1) z / z_k, so the taps it blends sit at these normalised weights;
+ *   2. depth: z = w0 z0 + w1 z1 + w2 z2; not visible unless near_z < z && z < far_z (NaN and degenerate vertices fall here);
+ *   3. screen position: s_k = (w_k z_k) / z, u = sum s_k u_k, v = sum s_k v_k: the inverse of the renderer's texel rule;
+ *   4. sample: px = 0.5f * ((u * S + S) - 1.0f), py alike from v, xi = floorf(px + 0.5f), yi = floorf(py + 0.5f); not visible
+ *      outside 0..S-1;
+ *   5. visible iff z <= depth[b, yi, xi] + depth_bias;
+ *   6. photo position, only if visible: align_corners == 0: qx = 0.5f * ((u * Wp + Wp) - 1.0f), qy = 0.5f * (((-v) * Wp + Wp) - 1.0f);
+ *      otherwise qx = ((u + 1) * 0.5f) * (Wp - 1), qy = ((1 - v) * 0.5f) * (Wp - 1) (grid_sample's align_corners=True).  In the
+ *      photo iff -0.5 <= qx <= Wp - 0.5 && -0.5 <= qy <= Hp - 0.5.  Colour: x0 = floorf(qx), fx = qx - x0, rows alike; the taps
+ *      x0, x0 + 1 clamped to 0..Wp-1 and y0, y0 + 1 to 0..Hp-1; top = a + (b - a) fx, bot = c + (d - c) fx, top + (bot - top) fy;
+ *   7. textures = the photo colour if visible and in the photo, else fallback[b,f]; texel_visible = steps 2-5, whatever 6 says.
+ * chore_point_visibility is steps 2, 4 and 5 on (u, v, z) = pts[b,n]: the same device function.
+ * Both calls are one kernel on `stream`: no workspace, no allocation, no atomics, no device value read by the host (they can be
+ * captured into a graph), bit-equal from call to call.  Index arithmetic is size_t.
+ * CHORE_EINVAL, before anything is launched: a NULL required pointer, B, F, N < 1, ts outside 2..16, S outside 1..4096, Hp < 1,
+ * Wp < 1, Hp > Wp.
+ * ------------------------------------------------------------------------------------------- */
+int chore_photo_textures_fwd(chore_handle* h, const float* tri, const float* depth, const float* photo,
+                             const float* fallback, int B, int F, int ts, int S, int Hp, int Wp,
+                             float near_z, float far_z, float depth_bias, int align_corners,
+                             float* textures, unsigned char* texel_visible, chore_stream_t stream);
+int chore_point_visibility(chore_handle* h, const float* pts, const float* depth, int B, int N, int S,
+                           float near_z, float far_z, float depth_bias, int* visible, chore_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Evaluation metrics, fp64 (replace recon/eval/chamfer_distance.py:10-52 = sklearn kd-tree nearest neighbours, and
  * recon/eval/pose_utils.py compute_transform :145-180 / compute_similarity_transform :103-143).
  *   chore_eval_chamfer   out[0] = mean_i min_j |x_i - y_j| (direction 'x_to_y'), out[1] = the other direction
