@@ -231,6 +231,10 @@ SIGNATURES = {
     "chore_instances_fwd": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_float] * 2 + [c_void_p] * 7),
     "chore_photo_textures_fwd": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_float] * 3 + [c_int] + [c_void_p] * 3),
     "chore_point_visibility": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_float] * 3 + [c_void_p] * 2),
+    "chore_load_textures": (c_int, [c_void_p] * 5 + [c_size_t] + [POINTER(c_int64), POINTER(c_int)] + [c_int] * 5 +
+                            [c_void_p] * 2),
+    "chore_texture_atlas_size": (c_int, [c_int, c_int, POINTER(c_int), POINTER(c_int)]),
+    "chore_texture_atlas": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "chore_mesh_dist_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "chore_mesh_dist_fwd": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 6),
     "chore_mesh_sdf_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),

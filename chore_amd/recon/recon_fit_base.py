@@ -365,7 +365,7 @@ class ReconFitterBase:
 
     def save_outputs(self, smpl, obj_R, obj_t, traindata_paths, save_name, test_id, obj_s=None, images=None, crop_centers=None):
         """fitted SMPL mesh + parameters and object mesh + parameters next to each other  [:258-275, opt_utils.py:73-101];
-        images (B,5,H,W) / crop_centers (B,2): the batch's, read by REPORT_DEPTH_ORDER only"""
+        images (B,5,H,W) / crop_centers (B,2): the batch's, read by REPORT_DEPTH_ORDER and EXPORT_TEXTURED_OBJ only"""
         smpl_files, obj_files = self.get_output_paths(traindata_paths, save_name, test_id)
         smpl.forget()
         with torch.no_grad():
@@ -413,6 +413,32 @@ class ReconFitterBase:
             for i, sf in enumerate(smpl_files):
                 with open(sf.replace(".smpl.ply", ".occlusion.json"), "w") as f:
                     json.dump(frame_report(*[c[i] for c in counts]), f, indent=1)
+        if self.EXPORT_TEXTURED_OBJ:            # the very meshes written above, wearing the photo; draws no random numbers
+            if faces is None or images is None or crop_centers is None:
+                raise RuntimeError("EXPORT_TEXTURED_OBJ needs the body model's faces and the batch's images and crop centres")
+            self._export_textured_obj(smpl_files, obj_files, verts, faces, obj_verts, images, crop_centers)
+
+    # ---- the fitted meshes as textured OBJ files (render/obj_io.py) ----------------------------------------------
+    # True: save_outputs (given the batch's images and crop centres) also writes k{test_id}.smpl.obj / .mtl / .png and
+    # k{test_id}.object.obj / .mtl / .png next to the PLY files: the vertices of the PLYs with the texture cubes
+    # utils/render_utils.render_photo_views draws (photo_mesh_textures), as a texture atlas any mesh viewer opens.  A texel the
+    # network's camera does not see has SMPL_OBJ_COLOR_LIST's colour, without the side view's light.  The fit itself never
+    # reads them: no fitted bit changes.
+    EXPORT_TEXTURED_OBJ = False
+
+    def _export_textured_obj(self, smpl_files, obj_files, verts, faces, obj_verts, images, crop_centers):
+        from ..render import save_obj
+        from ..utils.render_utils import SMPL_OBJ_COLOR_LIST, Mesh, mesh_tensors, photo_mesh_textures
+        dev = self.device
+        images, crop_centers = torch.as_tensor(images).to(dev), torch.as_tensor(crop_centers).to(dev)
+        for i, (sf, of) in enumerate(zip(smpl_files, obj_files)):
+            meshes = [Mesh(v=verts[i], f=faces), Mesh(v=obj_verts[i], f=self.scan.f)]
+            with torch.no_grad():
+                v, f, colour = mesh_tensors(meshes, SMPL_OBJ_COLOR_LIST, dev)
+                textures = photo_mesh_textures(images[i], crop_centers[i], v, f, colour[:, :, 0, 0, 0, :],
+                                               depth_bias=self.VIEW_POINT_BIAS, camera=self.camera)[0]
+            save_obj(sf.replace(".ply", ".obj"), verts[i], faces, textures[:len(faces)])
+            save_obj(of.replace(".ply", ".obj"), obj_verts[i], self.scan.f, textures[len(faces):])
 
     # ---- how much of the fitted object the fitted body hides (recon/eval/occlusion.py) --------------------------
     # The reference skips a frame whose object is less than 30 % visible (recon/evaluate.py:53-58) and reads that from mask

@@ -253,7 +253,7 @@ class ReconFitterBehave(ReconFitterBase):
         def finish(i, data, fitted):
             smpl, obj_R, obj_t, obj_s = fitted
             if save and self.outpath is not None:
-                if self.REPORT_DEPTH_ORDER:        # the report reads the batch's masks
+                if self.REPORT_DEPTH_ORDER or self.EXPORT_TEXTURED_OBJ:        # they read the batch's masks / photo
                     self.save_outputs(smpl, obj_R, obj_t, data["path"], args.save_name, args.test_kid, obj_s,
                                       images=data.get("images"), crop_centers=data.get("crop_center"))
                 else:

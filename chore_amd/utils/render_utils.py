@@ -432,6 +432,22 @@ def render_scene_views(images_b, crop_center_b, meshes, mesh_colors, mesh_opacit
     return np.concatenate([front, _side_crop(rgb, S)], axis=1)
 
 
+def photo_mesh_textures(images_b, crop_center_b, verts, faces, fallback, texture_size=TEXTURE_SIZE, depth_bias=0.02, camera=None):
+    """the texture cubes (1,F,ts,ts,ts,3) of camera-space meshes coloured from the photo they were fitted to: what
+    `render_photo_views` draws and what the fitter's textured OBJ export writes.  images_b (C,H,W) network input of the frame
+    (channels 0..2 RGB in [0,1]), crop_center_b (2,), verts (1,V,3) / faces (1,F,3) as `mesh_tensors` gives them, fallback
+    (1,F,3): the colour of a texel the network's camera does not see.  Every other texel takes the photo's colour
+    (`nr.photo_textures` on the `_input_view_ndc` triangles, align_corners=True like the network's own grid_sample, visibility
+    on the CLOUD_VIEW_SIZE grid over both windings)."""
+    camera = KinectColorCamera() if camera is None else camera
+    S, near, far = CLOUD_VIEW_SIZE, nr.renderer.DEFAULT_NEAR, nr.renderer.DEFAULT_FAR
+    ndc = _input_view_ndc(camera, verts[0], crop_center_b)
+    depth = nr.sample_depth(nr.vertices_to_faces(ndc, torch.cat((faces, faces.flip(-1)), dim=1)), S, near, far)
+    photo = images_b[:3].detach().float().clamp(0, 1)[None]
+    return nr.photo_textures(nr.vertices_to_faces(ndc, faces), depth, photo, fallback, texture_size, depth_bias, near, far,
+                             align_corners=True)
+
+
 def render_photo_views(images_b, crop_center_b, meshes, mesh_colors, texture_size=TEXTURE_SIZE, depth_bias=0.02, side_renderer=None,
                        camera=None, maxd=1.5):
     """the fitted meshes of ONE frame wearing the photo they were fitted to -> (512, 512 + 640, 3) uint8: the input photo on the
@@ -449,7 +465,7 @@ def render_photo_views(images_b, crop_center_b, meshes, mesh_colors, texture_siz
     dev = images_b.device
     camera = KinectColorCamera() if camera is None else camera
     verts, faces, textures = mesh_tensors(meshes, mesh_colors, dev)
-    S, near, far = CLOUD_VIEW_SIZE, nr.renderer.DEFAULT_NEAR, nr.renderer.DEFAULT_FAR
+    S = CLOUD_VIEW_SIZE
     blank = {"rgb": torch.zeros(1, 3, S, S, device=dev), "alpha": torch.zeros(1, S, S, device=dev)}
     front = _over_photo(blank, images_b, S)
 
@@ -459,11 +475,8 @@ def render_photo_views(images_b, crop_center_b, meshes, mesh_colors, texture_siz
     light = nr.face_light(nr.vertices_to_faces(side_verts, faces), side_renderer.light_intensity_ambient,
                           side_renderer.light_intensity_directional, side_renderer.light_color_ambient,
                           side_renderer.light_color_directional, side_renderer.light_direction)
-    ndc = _input_view_ndc(camera, verts[0], crop_center_b)
-    depth = nr.sample_depth(nr.vertices_to_faces(ndc, torch.cat((faces, faces.flip(-1)), dim=1)), S, near, far)
-    photo = images_b[:3].detach().float().clamp(0, 1)[None]
-    textures = nr.photo_textures(nr.vertices_to_faces(ndc, faces), depth, photo, textures[:, :, 0, 0, 0, :] * light, texture_size,
-                                 depth_bias, near, far, align_corners=True)
+    textures = photo_mesh_textures(images_b, crop_center_b, verts, faces, textures[:, :, 0, 0, 0, :] * light, texture_size,
+                                   depth_bias, camera)
     tri, tex, _, _ = side_renderer._prepare_faces(side_verts, faces, textures, (None,) * 5)
     rgb = nr.rasterize_rgbad(tri, tex, None, side_renderer.image_size, side_renderer.anti_aliasing, side_renderer.near,
                              side_renderer.far, side_renderer.rasterizer_eps, side_renderer.background_color)["rgb"]

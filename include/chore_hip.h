@@ -627,6 +627,63 @@ int chore_point_visibility(chore_handle* h, const float* pts, const float* depth
                            float near_z, float far_z, float depth_bias, int* visible, chore_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Textured OBJ files, forward only: texture cubes from UV triangles and texture images (neural_renderer's load_textures) and one
+ * image with a tile per face from texture cubes (neural_renderer's create_texture_image).  Both keep the reference's results
+ * wherever the reference is defined, and say what happens where it is not.
+ *
+ * chore_load_textures.  uv (F,3,2) fp32; face_image (F) int32: index into the image table, or negative; face_color (F,3) fp32;
+ * images: bytes on the device, all texture images back to back, each (H,W,3) RGB in file row order; images_bytes: their total;
+ * image_off (M) byte offset of each image in `images` and image_hw (M,2) its H, W: HOST arrays, read and checked before the launch
+ * and passed to the kernel by value; wrapping: 0 REPEAT, 1 MIRRORED_REPEAT, 2 CLAMP_TO_EDGE, 3 CLAMP_TO_BORDER; bilinear 0 / 1;
+ * textures (F,ts,ts,ts,3) fp32, chore_render_fwd's layout, every element written.  One launch for all materials.
+ * Texel (i,j,k) of face f; all arithmetic fp32, each operation rounded once (no contraction), sums of three from the left:
+ *   1. face_image[f] < 0 (or >= M): the texel is face_color[f].  Done.
+ *   2. wrapping == 3: the texel is 0.  (The reference writes zeros on every textured face in this mode and never samples; kept.)
+ *   3. weights: d = (i,j,k) / (ts-1), s = d0 + d1 + d2, and d /= s if s > 0.  The texel (0,0,0) keeps three zero weights and so
+ *      samples position (0,0): the reference's rule, not the 1/3 of chore_photo_textures_fwd.
+ *   4. wrap the six coordinates, in registers (the reference rewrites `uv` from every texel thread of a face; `uv` is const here):
+ *      mod(x,y) = x > 0 ? fmodf(x,y) : y + fmodf(x,y); REPEAT: mod(x,1), which sends 0 to 1 and 1 to 0 as in the reference;
+ *      MIRRORED_REPEAT: mod(x,2) < 1 ? mod(x,1) : 1 - mod(x,1); CLAMP_TO_EDGE: min(max(x,0),1).  A face with a non-finite
+ *      coordinate takes face_color[f] on every texel.
+ *   5. position: pos_x = (u0 d0 + u1 d1 + u2 d2) (W-1), pos_y alike from v with (H-1), measured in the vertically flipped image:
+ *      row r of the flipped image is row H-1-r of the image in `images` (flipped in the index; no copy is made).
+ *   6. bilinear: x0 = (int)pos_x, fx = pos_x - x0, x1 = x0 + 1, rows alike; a pixel is (float)byte / 255.0f;
+ *      top = a + (b - a) fx, bot = c + (d - c) fx, top + (bot - top) fy, so equal taps give their value exactly (the reference sums
+ *      four weighted taps).  Nearest: roundf (half away from zero).  In both modes every index is clamped to 0..W-1 / 0..H-1
+ *      before it is used (the reference's nearest mode and large bilinear positions are not): no load leaves the image.
+ * CHORE_EINVAL, before anything is launched: a NULL uv, face_image, face_color or textures; F < 1; ts outside 2..16; M < 0 or
+ * M > 128; with M > 0 a NULL images, image_off or image_hw, an H or W < 1, an image that does not lie inside images_bytes; a
+ * wrapping outside 0..3.
+ *
+ * chore_texture_atlas.  textures (F,tsi,tsi,tsi,3) fp32; image (tile_h tso, tile_w tso, 3) fp32 in file row order (the first
+ * row is the top of the picture), every element written.  Tile counts in integer arithmetic: tile_w = (int)sqrt(F-1) + 1,
+ * tile_h = (F-1) / tile_w + 1 (the reference's Python divides truly under torch >= 1.5).  chore_texture_atlas_size gives
+ * height = tile_h tso and width = tile_w tso, or CHORE_EINVAL where F < 1, tso < 2 or a side exceeds 16384 px.
+ * Pixel (x, y), y counted from the bottom of the picture (it is written to row height-1-y); fp32 as above:
+ *   1. col = x / tso, row = y / tso, fn = col + row tile_w, lx = x % tso, ly = y % tso, T = tso - 1.
+ *   2. fn >= F: the pixel is 0.  (The reference indexes faces that do not exist here.)
+ *   3. ly + 1 == lx: the steps below are evaluated at lx - 1.  (The reference's second kernel, which copies the left neighbour
+ *      into these pixels; folded in, so no pixel reads another thread's output.)
+ *   4. weights: w0 = ((T - ly) / T) / (1 + 1e-5f), w1 = ((ly - lx) / T) / (1 + 1e-5f), w2 = (lx / T) / (1 + 1e-5f): the
+ *      reference's face_inv (x, y, 1) / (sum + eps) for its tile triangle p0 = tile corner, p1 = p0 + (0,T), p2 = p0 + (T,T),
+ *      in tile-local coordinates (equal in exact arithmetic; accurate in fp32 at any atlas size, which the global form is not).
+ *   5. t_q = min(max(w_q (tsi-1), 0), tsi-1 - 1e-5f), i_q = (int)t_q, f_q = t_q - i_q, upper index min(i_q + 1, tsi-1).  The
+ *      pixel is the trilinear blend of the eight texels, in lerp form along k, then j, then i.
+ *   6. pixels above the diagonal (lx > ly + 1) go through the same steps with w1 clamped to 0, as in the reference.
+ * CHORE_EINVAL, before anything is launched: a NULL pointer, F < 1, tsi outside 2..16, tso < 2, a side above 16384 px.
+ *
+ * Both calls are one kernel on `stream`: no workspace, no allocation, no atomics, one writer per output element (bit-equal from
+ * call to call), no device value read by the host.  Index arithmetic is size_t.
+ * ------------------------------------------------------------------------------------------- */
+int chore_load_textures(chore_handle* h, const float* uv, const int* face_image, const float* face_color,
+                        const unsigned char* images, size_t images_bytes, const long long* image_off,
+                        const int* image_hw, int M, int F, int ts, int wrapping, int bilinear, float* textures,
+                        chore_stream_t stream);
+int chore_texture_atlas_size(int F, int tso, int* height, int* width);
+int chore_texture_atlas(chore_handle* h, const float* textures, int F, int tsi, int tso, float* image,
+                        chore_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Evaluation metrics, fp64 (replace recon/eval/chamfer_distance.py:10-52 = sklearn kd-tree nearest neighbours, and
  * recon/eval/pose_utils.py compute_transform :145-180 / compute_similarity_transform :103-143).
  *   chore_eval_chamfer   out[0] = mean_i min_j |x_i - y_j| (direction 'x_to_y'), out[1] = the other direction
